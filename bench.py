@@ -11,7 +11,12 @@ dense) stays available via --model llama3-8b. A step = one
 forward+backward+clip+optimizer over one synthetic packed seq-4096 batch
 per rank (weak scaling).
 
-Rank 0 prints ONE JSON line with metric/value/roofline/cpu_baseline.
+A plain run sets up, warms up, times --steps steps, writes its outputs if
+--dump-outputs is given, and prints the result line. --full adds the legs that
+take runs of their own: one profiled (untimed) step for the per-kernel
+roofline figure, and the CPU baseline; without it both fields are null.
+
+Rank 0 prints ONE JSON line with metric/value/ms_per_step/roofline/cpu_baseline.
 """
 
 import argparse
@@ -94,6 +99,47 @@ def run_cpu_baseline(preset, seq_len, budget_s=15.0):
     }
 
 
+DUMP_PER_TENSOR = 2048  # sampled elements per parameter tensor
+
+
+def dump_outputs(out_dir, loss, grad_norm, model, opt):
+    """Write what the last timed step handed back: its loss, its global grad
+    norm, and the state it left behind (updated parameters, AdamW first
+    moments). The big tensors are sampled: DUMP_PER_TENSOR seeded positions
+    per parameter, parameters in sorted-name order, so two builds write the
+    same positions (a few MB in all, float32)."""
+    import numpy as np
+    from torch.distributed.tensor import DTensor
+
+    def local(t):
+        return t.to_local() if isinstance(t, DTensor) else t
+
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(1234)
+    p_parts, m_parts = [], []
+    for _, p in sorted(model.named_parameters(), key=lambda kv: kv[0]):
+        flat = local(p.detach()).reshape(-1)
+        if flat.numel() == 0:
+            continue
+        idx = torch.randint(0, flat.numel(), (min(flat.numel(), DUMP_PER_TENSOR),),
+                            generator=g).to(flat.device)
+        p_parts.append(flat[idx].float().cpu())
+        m = opt.state.get(p, {}).get("exp_avg")
+        if m is not None:
+            m_parts.append(local(m.detach()).reshape(-1)[idx].float().cpu())
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu(),
+        "grad_norm": grad_norm.detach().float().reshape(1).cpu(),
+        "params_sample": torch.cat(p_parts),
+    }
+    if m_parts:
+        arrays["adam_exp_avg_sample"] = torch.cat(m_parts)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+    log("dumped " + ", ".join(f"{k}{tuple(v.shape)}" for k, v in arrays.items())
+        + f" to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -102,7 +148,15 @@ def main():
     ap.add_argument("--model", type=str, default=None)
     ap.add_argument("--seq-len", type=int, default=4096)
     ap.add_argument("--batch", type=int, default=0, help="micro-batch per rank (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the "
+                         "profiled step for the roofline field and the CPU "
+                         "baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one "
+                         "computed as DIR/<name>.npy")
     ap.add_argument("--sp", type=int, default=1,
                     help="Ulysses sequence-parallel degree (divides --gpus)")
     ap.add_argument("--checkpoint", choices=["auto", "on", "off"],
@@ -230,28 +284,31 @@ def main():
         loss = mean_global_loss(loss, n_valid)
         loss.backward()
         # fused path folds the clip coefficient into AdamW's grad_scale
-        model.clip_grad_norm_(1.0, fused_optimizer=opt if fused_ok else None)
+        gnorm = model.clip_grad_norm_(1.0, fused_optimizer=opt if fused_ok else None)
         opt.step()
         opt.zero_grad(set_to_none=True)
-        return loss
+        return loss, gnorm
 
     for i in range(args.warmup):
-        loss = one_step()
+        loss, _ = one_step()
         log(f"warmup {i}: loss {float(loss.detach()):.4f}")
 
-    # profile one extra (untimed) step for the per-kernel roofline leg
-    hip_lib.profile_enable(True)
-    one_step()
-    prof = hip_lib.profile_summary()
-    hip_lib.profile_enable(False)
+    prof = {}
+    if args.full:
+        # profile one extra (untimed) step for the per-kernel roofline leg
+        hip_lib.profile_enable(True)
+        one_step()
+        prof = hip_lib.profile_summary()
+        hip_lib.profile_enable(False)
 
     log(f"peak mem after warmup: {torch.cuda.max_memory_allocated()/2**30:.1f} GiB")
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.time()
+    last = None
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -276,7 +333,10 @@ def main():
         flops += 6.0 * p_vis * n_patches * n_gpus
     mfu = flops * args.steps / dt / (n_gpus * 2.5e15)
 
-    # roofline: dominant hand-written kernel
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last[0], last[1], model, opt)
+
+    # roofline: dominant hand-written kernel (--full only: prof is empty otherwise)
     roofline = None
     if "group_gemm_nk" in prof:
         rec = prof["group_gemm_nk"]
@@ -305,7 +365,8 @@ def main():
                     "kernel": "vh_ce_fwd_bf16"}
 
     cpu_baseline = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not is_vl:
+    if (args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline
+            and not is_vl):
         log("timing CPU baseline (host cores, bounded sample)")
         try:
             cpu_baseline = run_cpu_baseline(preset, seq)

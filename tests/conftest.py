@@ -7,6 +7,9 @@ import torch
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO_ROOT not in sys.path:
     sys.path.insert(0, REPO_ROOT)
+TESTS_DIR = os.path.dirname(os.path.abspath(__file__))
+if TESTS_DIR not in sys.path:  # `golden.shards` (fixture loader) lives here
+    sys.path.insert(0, TESTS_DIR)
 
 
 def pytest_configure(config):
@@ -24,5 +27,7 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def golden():
-    path = os.path.join(os.path.dirname(__file__), "golden", "golden.pt")
-    return torch.load(path, weights_only=False)
+    # the fixture is stored as golden.NNN.pt shards (tests/golden/shards.py)
+    from golden.shards import load_sharded
+
+    return load_sharded(os.path.join(os.path.dirname(__file__), "golden", "golden"))

@@ -6,7 +6,7 @@ only in the build container — never on the GPU box) and executes its own
 eager CPU code paths on seeded inputs. The outputs are committed as small
 fixtures (golden.pt) so parity tests never need the reference at run time.
 
-Usage:  python tests/golden/make_golden.py          # writes tests/golden/golden.pt
+Usage:  python tests/golden/make_golden.py   # writes tests/golden/golden.NNN.pt shards
 
 Every entry records the reference call site it exercises.
 """
@@ -387,6 +387,9 @@ for st in range(3):
     step_losses.append(out2.loss.detach())
 golden["train3/losses"] = torch.stack(step_losses)
 
-out_path = os.path.join(os.path.dirname(__file__), "golden.pt")
-torch.save(golden, out_path)
-print(f"wrote {out_path} with {len(golden)} entries")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from shards import save_sharded  # noqa: E402
+
+out_paths = save_sharded(
+    golden, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+print(f"wrote {len(out_paths)} shards with {len(golden)} entries")

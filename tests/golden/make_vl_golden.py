@@ -7,7 +7,7 @@ vision features so our VLM's parity tests never need the reference at run
 time. Anchor: /root/reference/veomni/models/transformers/qwen2_5vl/generated/
 patched_modeling_qwen2_5_vl_gpu.py.
 
-Usage: python tests/golden/make_vl_golden.py  -> tests/golden/vl_golden.pt
+Usage: python tests/golden/make_vl_golden.py  -> tests/golden/vl_golden.NNN.pt shards
 """
 
 import os
@@ -97,6 +97,9 @@ golden = {
     "state_dict": {k: v.clone() for k, v in model.state_dict().items()},
 }
 
-out_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "vl_golden.pt")
-torch.save(golden, out_path)
-print(f"wrote {out_path} ({os.path.getsize(out_path)/2**20:.1f} MiB)")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from shards import save_sharded  # noqa: E402
+
+out_paths = save_sharded(
+    golden, os.path.join(os.path.dirname(os.path.abspath(__file__)), "vl_golden"))
+print(f"wrote {len(out_paths)} shards")

@@ -24,6 +24,41 @@ def test_step_flops_scales_linearly_in_tokens():
     assert abs(f2 / f1 - 2.0) < 1e-6
 
 
+def test_dump_outputs_is_deterministic_float_npy(tmp_path):
+    """--dump-outputs writer: float32 .npy files, the same sampled positions
+    on every call, parameters and AdamW moments sampled alike."""
+    import numpy as np
+    import torch
+
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(64, 96), torch.nn.Linear(96, 8))
+    opt = torch.optim.AdamW(model.parameters(), lr=1e-2)
+    loss = model(torch.randn(4, 64)).square().mean()
+    loss.backward()
+    gnorm = torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
+    opt.step()
+
+    bench.dump_outputs(str(tmp_path / "a"), loss, gnorm, model, opt)
+    bench.dump_outputs(str(tmp_path / "b"), loss, gnorm, model, opt)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["adam_exp_avg_sample.npy", "grad_norm.npy", "loss.npy",
+                     "params_sample.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        assert np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total < 64 * 2**20
+    ps = np.load(tmp_path / "a" / "params_sample.npy")
+    # 4 tensors: 64*96 and 96*8 weights are capped, the biases are sampled
+    # with replacement at their own size
+    cap = bench.DUMP_PER_TENSOR
+    assert ps.shape == (min(64 * 96, cap) + 96 + min(96 * 8, cap) + 8,)
+    assert np.load(tmp_path / "a" / "adam_exp_avg_sample.npy").shape == ps.shape
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == float(loss.detach())
+
+
 def test_moe_preset_matches_qwen3_30b_a3b_card():
     c = PRESETS["qwen3-moe-30b"]
     assert (c.num_hidden_layers, c.hidden_size, c.num_experts,

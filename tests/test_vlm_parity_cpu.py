@@ -1,4 +1,4 @@
-"""Qwen2.5-VL parity vs the committed reference golden (vl_golden.pt:
+"""Qwen2.5-VL parity vs the committed reference golden (vl_golden.NNN.pt:
 weights + inputs + logits + vision features + 3D rope index, produced by
 RUNNING the reference patched modeling — tests/golden/make_vl_golden.py)."""
 
@@ -7,12 +7,14 @@ import os
 import pytest
 import torch
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "vl_golden.pt")
+GOLD = os.path.join(os.path.dirname(__file__), "golden", "vl_golden")
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return torch.load(GOLD, weights_only=False)
+    from golden.shards import load_sharded
+
+    return load_sharded(GOLD)
 
 
 def _load_reference_weights(model, sd):

@@ -264,6 +264,48 @@ int vh_ce_fwd_bf16(const uint16_t* logits, const int64_t* labels,
                    int64_t V, float grad_scale, int64_t ignore_index,
                    void* stream);
 
+/* ---- Fused MoE load-balancing (aux) loss --------------------------------- */
+
+/* Switch-transformer aux loss over per-layer router logits [T, E] with
+ * contiguous rows; dtype: 0 = bf16, 1 = fp32; 1 <= top_k <= E <= 256.
+ * Replaces the reference's fused provider
+ * (load_balancing_loss/triton.py:280-354; semantics eager.py:28-114).
+ * Per row: fp32 upcast, max-subtracted softmax p, prob_sum += w*p, and each
+ * of the top_k selected experts gets count += w (w = mask_w[t], or 1 when
+ * mask_w is null).
+ * SELECTION RULE: the top_k largest LOGITS of the row after the upcast, ties
+ * to the LOWEST expert index -- equal to the reference's top-k of the
+ * probabilities wherever that is unambiguous, and independent of the exp
+ * implementation. -inf logits are allowed (p = 0); NaN logits and all--inf
+ * rows are outside the contract.
+ *
+ * Forward, stage 1: launches exactly P blocks that grid-stride over rows;
+ * block b writes partial[b,0,:] = weighted expert counts and partial[b,1,:]
+ * = weighted probability sums of its rows (zeros if it had none). No
+ * atomics: bit-reproducible run to run. partial: fp32 [P, 2, E]. */
+int vh_lbl_fwd(const void* logits, int dtype, const float* mask_w, int64_t T,
+               int E, int top_k, float* partial, int P, void* stream);
+
+/* Forward, stage 2: reduces the P_total partial rows of all layers in fixed
+ * row order (double accumulation: counts stay exact past 2^24; results
+ * stored fp32) into count [E] / prob_sum [E], then out[1] = coef =
+ * E / total_w^2 and out[0] = loss = dot(count, prob_sum) * coef; both are 0
+ * when total_w == 0 (the reference's early return, without a host sync).
+ * total_w: device fp32 [1]. */
+int vh_lbl_finish(const float* partial, int64_t P_total, int E,
+                  const float* total_w, float* count, float* prob_sum,
+                  float* out, void* stream);
+
+/* Backward for one layer (recomputes the row softmax):
+ *   grad[t,j] = grad_out*coef*w_t * p_j * (count_j - sum_i p_i count_i),
+ * evaluated in fp32 and rounded once to the logits dtype; rows with
+ * w_t == 0 get zeros. coef / grad_out: device fp32 [1]; grad_logits [T, E]
+ * in the logits dtype.
+ * Replaces triton.py's backward kernel (same formula). */
+int vh_lbl_bwd(const void* logits, int dtype, const float* mask_w,
+               const float* count, const float* coef, const float* grad_out,
+               void* grad_logits, int64_t T, int E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

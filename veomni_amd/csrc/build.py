@@ -23,6 +23,7 @@ SOURCES = [
     "vh_attention.hip",
     "vh_ce.hip",
     "vh_adamw.hip",
+    "vh_lbl.hip",
 ]
 
 

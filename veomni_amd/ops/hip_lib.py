@@ -82,6 +82,9 @@ def get_lib() -> ctypes.CDLL:
          c_int, c_int, c_int, c_i64, c_f32, c_p)
     _sig(lib, "vh_attn_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
+    _sig(lib, "vh_lbl_fwd", c_p, c_int, c_p, c_i64, c_int, c_int, c_p, c_int, c_p)
+    _sig(lib, "vh_lbl_finish", c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p)
+    _sig(lib, "vh_lbl_bwd", c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_p)
     _LIB = lib
     return lib
 
@@ -407,3 +410,97 @@ def attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                     dptr(doc_end) if doc_end is not None else None,
                                     cur_stream()), "vh_attn_bwd2")
     return dq, dk, dv
+
+
+# ---------------------------------------------------- load-balancing loss
+# vh_lbl_fwd geometry: 1024-thread blocks, a sub-group of G lanes per row
+# (G = pow2 >= ceil(E/8)), so one block pass covers 1024/G rows. At most
+# LBL_MAX_BLOCKS blocks per layer (one per CU) grid-stride over the rows; the
+# cap also bounds the partial rows the finish pass has to read.
+LBL_FWD_THREADS = 1024
+LBL_MAX_BLOCKS = 256
+_LBL_DTYPES = {torch.bfloat16: 0, torch.float32: 1}
+
+
+def lbl_rows_per_block(num_experts: int) -> int:
+    groups, g = (num_experts + 7) // 8, 1
+    while g < groups:
+        g *= 2
+    return max(LBL_FWD_THREADS // g, 1)
+
+
+def lbl_num_blocks(rows: int, num_experts: int) -> int:
+    rpb = lbl_rows_per_block(num_experts)
+    return min((rows + rpb - 1) // rpb, LBL_MAX_BLOCKS)
+
+
+def _lbl_dtype(t: torch.Tensor) -> int:
+    if t.dtype not in _LBL_DTYPES:
+        raise TypeError(f"load_balancing_loss: logits dtype {t.dtype} "
+                        "(bf16 and fp32 are supported)")
+    return _LBL_DTYPES[t.dtype]
+
+
+def lbl_fwd(layers, top_k: int, mask_w: torch.Tensor | None,
+            total_w: torch.Tensor | None = None):
+    """Aux-loss forward over per-layer router logits [T_l, E] (contiguous,
+    one dtype, one device). mask_w: fp32 [T] per-row weights shared by every
+    layer, or None. total_w: device fp32 [1] normaliser (default: the summed
+    row weights). Returns (loss 0-dim, count [E], prob_sum [E], coef [1]),
+    all fp32. One vh_lbl_fwd per non-empty layer into its slice of a shared
+    partial buffer, then one vh_lbl_finish; the layers are never
+    concatenated."""
+    layers = [l for l in layers if l.shape[0] > 0]  # 0-row layers are skipped
+    assert layers, "lbl_fwd needs at least one non-empty layer"
+    dev = layers[0].device
+    E = layers[0].shape[1]
+    blocks = [lbl_num_blocks(l.shape[0], E) for l in layers]
+    p_total = sum(blocks)
+    partial = torch.empty(p_total, 2, E, dtype=torch.float32, device=dev)
+    count = torch.empty(E, dtype=torch.float32, device=dev)
+    prob_sum = torch.empty(E, dtype=torch.float32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    if total_w is None:
+        if mask_w is not None:
+            total_w = (mask_w.sum() * len(layers)).reshape(1)
+        else:
+            total_w = torch.full((1,), float(sum(l.shape[0] for l in layers)),
+                                 dtype=torch.float32, device=dev)
+    lib = get_lib()
+    stream = cur_stream()
+    nbytes = sum(l.numel() * l.element_size() for l in layers)
+    with _prof("lbl_fwd", float(nbytes)):
+        row0 = 0
+        for l, P in zip(layers, blocks):
+            T = l.shape[0]
+            assert l.is_contiguous() and l.shape[1] == E
+            if mask_w is not None:
+                assert mask_w.numel() == T, (mask_w.numel(), T)
+            check(lib.vh_lbl_fwd(dptr(l), _lbl_dtype(l),
+                                 dptr(mask_w) if mask_w is not None else None,
+                                 T, E, top_k, dptr(partial[row0]), P, stream),
+                  "vh_lbl_fwd")
+            row0 += P
+        check(lib.vh_lbl_finish(dptr(partial), p_total, E, dptr(total_w),
+                                dptr(count), dptr(prob_sum), dptr(out), stream),
+              "vh_lbl_finish")
+    return out[0], count, prob_sum, out[1:2]
+
+
+def lbl_bwd(layer: torch.Tensor, mask_w: torch.Tensor | None,
+            count: torch.Tensor, coef: torch.Tensor,
+            grad_out: torch.Tensor) -> torch.Tensor:
+    """Gradient of the aux loss w.r.t. one layer's logits (same dtype).
+    coef / grad_out are device fp32 scalars (no host sync)."""
+    grad = torch.empty_like(layer)
+    T, E = layer.shape
+    if T == 0:
+        return grad
+    assert layer.is_contiguous() and grad.is_contiguous()
+    with _prof("lbl_bwd", 2.0 * layer.numel() * layer.element_size()):
+        check(get_lib().vh_lbl_bwd(dptr(layer), _lbl_dtype(layer),
+                                   dptr(mask_w) if mask_w is not None else None,
+                                   dptr(count), dptr(coef), dptr(grad_out),
+                                   dptr(grad), T, E, cur_stream()),
+              "vh_lbl_bwd")
+    return grad

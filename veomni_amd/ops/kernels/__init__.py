@@ -1,1 +1,1 @@
-from . import attention, cross_entropy, moe, norms  # noqa: F401
+from . import attention, cross_entropy, load_balancing_loss, moe, norms  # noqa: F401

@@ -160,7 +160,40 @@ int vh_moe_silu_mul_weighted_bwd_bf16(const uint16_t* dy, const uint16_t* fc1,
                                       float* dw_row, int64_t rows, int64_t I,
                                       int has_w, void* stream);
 
-/* ---- RMSNorm ------------------------------------------------------------ */
+/* Clamped SwiGLU (`swiglu_limit`, gpt-oss / DeepSeek-V4) variants of the two
+ * entries above; same buffers, plus the limit L before the stream.
+ * Replaces: ops/kernels/moe/group_gemm.py:24-42 and its uses at :357-363,
+ * :477-480 (clamp + two boolean masks, saved for backward).
+ * With g_raw/u_raw the raw halves of fc1:
+ *   g = min(g_raw, L);  u = min(max(u_raw, -L), L);
+ *   forward : act = silu(g) * u * w_row, the rounding chain of the unclamped
+ *             entry (silu -> bf16, *u -> bf16, *w -> bf16);
+ *   backward: dg = (g_raw <= L)        ? dy*w*u*silu'(g) : 0
+ *             du = (-L <= u_raw <= L)  ? dy*w*silu(g)    : 0
+ *             dw_row[t] = sum_i dy*silu(g)*u  (clamped g, u).
+ * Bounds are inclusive: a value exactly at +-L passes its gradient, as
+ * torch.clamp autograd does. Backward takes the RAW fc1 and recomputes clamp
+ * and mask; no mask or clamped copy is ever written. dw_row is STORED (one
+ * wave owns a row), so it needs no zero fill. rows == 0 is a no-op returning
+ * 0. Nonzero return if I % 8 != 0 or L is not finite and > 0.
+ * L is used as received. bf16 callers pass the limit rounded to bf16
+ * (round-to-nearest-even): that is the value the reference's bf16 `clamp` and
+ * `<=` against a Python scalar effectively use — e.g. bf16 x = 7.125 with
+ * limit 7.12 has x <= limit true, clamp(max=limit) = 7.125 and the gradient
+ * passes. hip_lib does this rounding. */
+int vh_moe_silu_mul_clamp_weighted_bf16(const uint16_t* fc1,
+                                        const uint16_t* w_row, uint16_t* out,
+                                        int64_t rows, int64_t I, int has_w,
+                                        float limit, void* stream);
+
+int vh_moe_silu_mul_clamp_weighted_bwd_bf16(const uint16_t* dy,
+                                            const uint16_t* fc1,
+                                            const uint16_t* w_row,
+                                            uint16_t* dfc1, float* dw_row,
+                                            int64_t rows, int64_t I, int has_w,
+                                            float limit, void* stream);
+
+/* ---- RMSNorm------------------------------------------------------------ */
 
 /* y = w * cast_bf16(x_f32 * rsqrt(mean(x^2)+eps)); saves rstd fp32 [T].
  * Replaces the Liger RMSNorm slot (ref ops/liger/__init__.py:28-60); math

@@ -17,6 +17,7 @@ OUT = os.path.join(PKG, "libveomni_hip.so")
 SOURCES = [
     "vh_abi.cpp",
     "vh_moe_ops.hip",
+    "vh_moe_swiglu_limit.hip",
     "vh_group_gemm.hip",
     "vh_group_gemm8.hip",
     "vh_norms.hip",

@@ -61,6 +61,9 @@ class ModelConfig:
     moe_intermediate_size: int = 768
     norm_topk_prob: bool = True
     router_aux_loss_coef: float = 0.0  # >0 enables the aux loss path
+    # clamped SwiGLU in the experts (gpt-oss / DeepSeek-V4): gate <= L,
+    # -L <= up <= L before silu(gate) * up; None = plain SwiGLU
+    swiglu_limit: Optional[float] = None
     # multimodal (Qwen2.5-VL) 3D-RoPE channel sections (t, h, w); None = 1D
     mrope_section: Optional[tuple] = None
     name: str = "model"
@@ -385,13 +388,16 @@ class _EagerEPExperts:
     post-down_proj weighting)."""
 
     @staticmethod
-    def apply(permute_tokens, cumsum, gate_up_w, down_w):
+    def apply(permute_tokens, cumsum, gate_up_w, down_w, limit=None):
         outs = []
         start = 0
         for g in range(gate_up_w.shape[0]):
             end = int(cumsum[g])
             cur = permute_tokens[start:end]
             gate, up = F.linear(cur, gate_up_w[g]).chunk(2, dim=-1)
+            if limit is not None:
+                gate = gate.clamp(max=limit)
+                up = up.clamp(min=-limit, max=limit)
             outs.append(F.linear(F.silu(gate) * up, down_w[g]))
             start = end
         return torch.cat(outs, dim=0)
@@ -405,6 +411,8 @@ class Experts(nn.Module):
         self.num_experts = config.num_experts
         self.hidden_dim = config.hidden_size
         self.intermediate_dim = config.moe_intermediate_size
+        # swiglu limit, under the attribute name the moe_experts adapter reads
+        self.limit = config.swiglu_limit
         self.gate_up_proj = nn.Parameter(
             torch.empty(self.num_experts, 2 * self.intermediate_dim, self.hidden_dim)
         )
@@ -422,9 +430,10 @@ class Experts(nn.Module):
             # below would index out of range)
             from ..distributed.moe import dispatch_to_ep_class
 
+            limit_arg = () if self.limit is None else (self.limit,)
             return dispatch_to_ep_class(
                 _EagerEPExperts, self.num_experts, top_k_weights, top_k_index,
-                hidden_states, self.gate_up_proj, self.down_proj)
+                hidden_states, self.gate_up_proj, self.down_proj, *limit_arg)
         # eager loop — weights applied AFTER down_proj (ref :266-294)
         final = torch.zeros_like(hidden_states)
         with torch.no_grad():
@@ -436,6 +445,9 @@ class Experts(nn.Module):
             cur = hidden_states[token_idx]
             gate_up = F.linear(cur, self.gate_up_proj[e])
             gate, up = gate_up.chunk(2, dim=-1)
+            if self.limit is not None:
+                gate = gate.clamp(max=self.limit)
+                up = up.clamp(min=-self.limit, max=self.limit)
             h = F.silu(gate) * up
             h = F.linear(h, self.down_proj[e])
             h = h * top_k_weights[token_idx, top_k_pos, None]

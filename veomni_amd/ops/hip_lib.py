@@ -66,6 +66,10 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_moe_silu_mul_weighted_bf16", c_p, c_p, c_p, c_i64, c_i64, c_int, c_p)
     _sig(lib, "vh_moe_silu_mul_weighted_bwd_bf16", c_p, c_p, c_p, c_p, c_p,
          c_i64, c_i64, c_int, c_p)
+    _sig(lib, "vh_moe_silu_mul_clamp_weighted_bf16", c_p, c_p, c_p, c_i64, c_i64,
+         c_int, c_f32, c_p)
+    _sig(lib, "vh_moe_silu_mul_clamp_weighted_bwd_bf16", c_p, c_p, c_p, c_p, c_p,
+         c_i64, c_i64, c_int, c_f32, c_p)
     _sig(lib, "vh_rmsnorm_fwd_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p)
     _sig(lib, "vh_rmsnorm_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p)
     _sig(lib, "vh_rope_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64,
@@ -265,11 +269,27 @@ def weight_transpose(b: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def silu_mul_weighted(fc1: torch.Tensor, w_row: torch.Tensor | None) -> torch.Tensor:
+def swiglu_limit_bf16(limit: float) -> float:
+    """The limit as the clamped kernels receive it: rounded to bf16
+    (round-to-nearest-even). A bf16 `clamp` / `<=` against a Python scalar
+    behaves as if the scalar had this value (bf16 7.125 <= 7.12 is True)."""
+    return float(torch.tensor(limit, dtype=torch.bfloat16))
+
+
+def silu_mul_weighted(fc1: torch.Tensor, w_row: torch.Tensor | None,
+                      limit: float | None = None) -> torch.Tensor:
+    """silu(gate) * up * w_row over merged fc1 [rows, 2I]; with `limit` the
+    clamped-SwiGLU entry (gate <= L, -L <= up <= L, L = bf16(limit))."""
     rows, twoI = fc1.shape
     I = twoI // 2
     out = torch.empty(rows, I, dtype=fc1.dtype, device=fc1.device)
     has_w = w_row is not None
+    if limit is not None:
+        check(get_lib().vh_moe_silu_mul_clamp_weighted_bf16(
+            dptr(fc1.contiguous()), dptr(w_row.contiguous()) if has_w else None,
+            dptr(out), rows, I, int(has_w), swiglu_limit_bf16(limit),
+            cur_stream()), "vh_moe_silu_mul_clamp_weighted")
+        return out
     check(get_lib().vh_moe_silu_mul_weighted_bf16(
         dptr(fc1.contiguous()), dptr(w_row.contiguous()) if has_w else None,
         dptr(out), rows, I, int(has_w), cur_stream()), "vh_moe_silu_mul_weighted")
@@ -277,11 +297,24 @@ def silu_mul_weighted(fc1: torch.Tensor, w_row: torch.Tensor | None) -> torch.Te
 
 
 def silu_mul_weighted_bwd(dy: torch.Tensor, fc1: torch.Tensor,
-                          w_row: torch.Tensor | None):
+                          w_row: torch.Tensor | None,
+                          limit: float | None = None):
+    """Backward of silu_mul_weighted from the RAW saved fc1: (dfc1, dw_row).
+    With `limit`, clamp and gradient mask are recomputed in the kernel and
+    dw_row is stored, not accumulated, so it is allocated uninitialised."""
     rows, twoI = fc1.shape
     I = twoI // 2
     dfc1 = torch.empty_like(fc1)
     has_w = w_row is not None
+    if limit is not None:
+        dw_row = torch.empty(rows, dtype=torch.float32, device=fc1.device) if has_w else None
+        check(get_lib().vh_moe_silu_mul_clamp_weighted_bwd_bf16(
+            dptr(dy.contiguous()), dptr(fc1.contiguous()),
+            dptr(w_row.contiguous()) if has_w else None, dptr(dfc1),
+            dptr(dw_row) if has_w else None, rows, I, int(has_w),
+            swiglu_limit_bf16(limit), cur_stream()),
+            "vh_moe_silu_mul_clamp_weighted_bwd")
+        return dfc1, dw_row
     dw_row = torch.zeros(rows, dtype=torch.float32, device=fc1.device) if has_w else None
     check(get_lib().vh_moe_silu_mul_weighted_bwd_bf16(
         dptr(dy.contiguous()), dptr(fc1.contiguous()),

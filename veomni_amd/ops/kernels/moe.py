@@ -13,9 +13,19 @@ Parity targets:
 
 Device work: vh_expert_histogram / vh_moe_scatter / vh_group_gemm_nk /
 vh_moe_silu_mul_weighted / vh_group_gemm_mn / vh_moe_gather (C ABI).
+
+Clamped SwiGLU (`swiglu_limit`; ref group_gemm.py:24-42, :357-363, :477-480):
+every expert path takes an optional limit and hands it to the epilogue pair,
+which then runs vh_moe_silu_mul_clamp_weighted(_bwd). The saved tensor is
+still the RAW fc1 — clamp and gradient mask are recomputed in the backward
+kernel, nothing extra is saved. With limit None every path issues exactly the
+calls it issued before the limit existed.
 """
 
 from __future__ import annotations
+
+import functools
+import math
 
 import torch
 
@@ -42,7 +52,7 @@ class HipFusedMoeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, num_experts, gate_weights, expert_index, hidden_states,
-                fc1_1_2_weight, fc2_weight):
+                fc1_1_2_weight, fc2_weight, swiglu_limit=None):
         T, H = hidden_states.shape
         splits = hip_lib.expert_histogram(expert_index, num_experts)
         _, scatter_index = compute_expert_scatter_index(expert_index)
@@ -54,12 +64,13 @@ class HipFusedMoeFunction(torch.autograd.Function):
         w = gate_weights.reshape(-1)
         scattered_w = torch.empty_like(w)
         scattered_w[scatter_index.flatten().to(torch.int64)] = w
-        weighted = hip_lib.silu_mul_weighted(fc1, scattered_w)
+        weighted = hip_lib.silu_mul_weighted(fc1, scattered_w, swiglu_limit)
 
         fc2 = hip_lib.group_gemm_nk(weighted, fc2_weight, cumsum_t, trans_b=True)
         out = hip_lib.moe_gather(fc2, scatter_index)
 
         ctx.num_experts = num_experts
+        ctx.swiglu_limit = swiglu_limit
         ctx.save_for_backward(gate_weights, fc1_1_2_weight, fc2_weight,
                               scatter_index, scatter_output, cumsum_t, fc1,
                               scattered_w, weighted)
@@ -81,8 +92,10 @@ class HipFusedMoeFunction(torch.autograd.Function):
         # wgrad fc2: [G, H, I]
         d_fc2_w = hip_lib.group_gemm_mn(grad_fc2_out, weighted, cumsum_t, G)
 
-        # fused epilogue backward (silu recomputed from saved pre-activation)
-        d_fc1, dw_rows = hip_lib.silu_mul_weighted_bwd(d_weighted, fc1, scattered_w)
+        # fused epilogue backward (silu — and, with a limit, clamp + mask —
+        # recomputed from the saved raw pre-activation)
+        d_fc1, dw_rows = hip_lib.silu_mul_weighted_bwd(d_weighted, fc1, scattered_w,
+                                                       ctx.swiglu_limit)
         grad_gate = dw_rows[scatter_index.flatten().to(torch.int64)]
         grad_gate = grad_gate.reshape(gate_weights.shape).to(gate_weights.dtype)
 
@@ -92,7 +105,7 @@ class HipFusedMoeFunction(torch.autograd.Function):
         d_fc1_w = hip_lib.group_gemm_mn(d_fc1, scatter_output, cumsum_t, G)
 
         grad_hidden = hip_lib.moe_gather(d_scatter, scatter_index)
-        return None, grad_gate, None, grad_hidden, d_fc1_w, d_fc2_w
+        return None, grad_gate, None, grad_hidden, d_fc1_w, d_fc2_w, None
 
 
 class EPMergedFc1HipGroupGemm(torch.autograd.Function):
@@ -103,10 +116,12 @@ class EPMergedFc1HipGroupGemm(torch.autograd.Function):
     wgrad/a2a backward overlap)."""
 
     @staticmethod
-    def forward(ctx, permute_tokens, cumsum, fc1_1_2_weight, fc2_weight):
+    def forward(ctx, permute_tokens, cumsum, fc1_1_2_weight, fc2_weight,
+                swiglu_limit=None):
         fc1 = hip_lib.group_gemm_nk(permute_tokens, fc1_1_2_weight, cumsum, trans_b=True)
-        act = hip_lib.silu_mul_weighted(fc1, None)
+        act = hip_lib.silu_mul_weighted(fc1, None, swiglu_limit)
         fc2 = hip_lib.group_gemm_nk(act, fc2_weight, cumsum, trans_b=True)
+        ctx.swiglu_limit = swiglu_limit
         ctx.save_for_backward(permute_tokens, cumsum, fc1_1_2_weight, fc2_weight, fc1, act)
         return fc2
 
@@ -118,28 +133,28 @@ class EPMergedFc1HipGroupGemm(torch.autograd.Function):
         d_act = hip_lib.group_gemm_nk(
             grad_output, hip_lib.weight_transpose(fc2_weight), cumsum, trans_b=True)
         d_fc2_w = hip_lib.group_gemm_mn(grad_output, act, cumsum, G)
-        d_fc1, _ = hip_lib.silu_mul_weighted_bwd(d_act, fc1, None)
+        d_fc1, _ = hip_lib.silu_mul_weighted_bwd(d_act, fc1, None, ctx.swiglu_limit)
         d_tokens = hip_lib.group_gemm_nk(
             d_fc1, hip_lib.weight_transpose(fc1_1_2_weight), cumsum, trans_b=True)
         d_fc1_w = hip_lib.group_gemm_mn(d_fc1, permute_tokens, cumsum, G)
-        return d_tokens, None, d_fc1_w, d_fc2_w
+        return d_tokens, None, d_fc1_w, d_fc2_w, None
 
 
 # ---- overlapped EP class: dispatch a2a owned by the autograd node so its
 # backward launches the return exchange before the wgrad GEMMs ------------
 
-def _ep_mlp_fwd(tokens, cumsum, fc1_1_2_weight, fc2_weight):
+def _ep_mlp_fwd(tokens, cumsum, fc1_1_2_weight, fc2_weight, swiglu_limit=None):
     fc1 = hip_lib.group_gemm_nk(tokens, fc1_1_2_weight, cumsum, trans_b=True)
-    act = hip_lib.silu_mul_weighted(fc1, None)
+    act = hip_lib.silu_mul_weighted(fc1, None, swiglu_limit)
     fc2 = hip_lib.group_gemm_nk(act, fc2_weight, cumsum, trans_b=True)
     return fc2, (tokens, fc1_1_2_weight, fc2_weight, fc1, act)
 
 
-def _ep_mlp_bwd_dgrad(dY, cumsum, saved):
+def _ep_mlp_bwd_dgrad(dY, cumsum, saved, swiglu_limit=None):
     _, w1, w2, fc1, _ = saved
     d_act = hip_lib.group_gemm_nk(dY, hip_lib.weight_transpose(w2), cumsum,
                                   trans_b=True)
-    d_fc1, _ = hip_lib.silu_mul_weighted_bwd(d_act, fc1, None)
+    d_fc1, _ = hip_lib.silu_mul_weighted_bwd(d_act, fc1, None, swiglu_limit)
     d_tokens = hip_lib.group_gemm_nk(d_fc1, hip_lib.weight_transpose(w1),
                                      cumsum, trans_b=True)
     return d_tokens, (dY, d_fc1)
@@ -154,13 +169,44 @@ def _ep_mlp_bwd_wgrad(cumsum, saved, stash):
     return (d_fc1_w, d_fc2_w)
 
 
-def _make_ep_a2a():
+def _make_ep_a2a(swiglu_limit=None):
     from ...distributed.moe import make_ep_a2a_class
 
-    return make_ep_a2a_class(_ep_mlp_fwd, _ep_mlp_bwd_dgrad, _ep_mlp_bwd_wgrad)
+    if swiglu_limit is None:
+        return make_ep_a2a_class(_ep_mlp_fwd, _ep_mlp_bwd_dgrad, _ep_mlp_bwd_wgrad)
+    # the class takes closures, so the limit rides in them (the wgrad leg
+    # never sees the activation and needs none)
+    return make_ep_a2a_class(
+        functools.partial(_ep_mlp_fwd, swiglu_limit=swiglu_limit),
+        functools.partial(_ep_mlp_bwd_dgrad, swiglu_limit=swiglu_limit),
+        _ep_mlp_bwd_wgrad)
 
 
 EPMergedFc1HipGroupGemmA2A = _make_ep_a2a()
+
+
+@functools.lru_cache(maxsize=None)
+def ep_a2a_class_for_limit(swiglu_limit=None):
+    """The overlapped EP class for a given swiglu_limit, built once per
+    value. None is the module-level EPMergedFc1HipGroupGemmA2A itself."""
+    if swiglu_limit is None:
+        return EPMergedFc1HipGroupGemmA2A
+    return _make_ep_a2a(float(swiglu_limit))
+
+
+def check_swiglu_limit(swiglu_limit):
+    """None, or a finite number > 0 (returned as float); else ValueError."""
+    if swiglu_limit is None:
+        return None
+    try:
+        ok = not isinstance(swiglu_limit, bool) and math.isfinite(swiglu_limit) \
+            and swiglu_limit > 0
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(
+            f"swiglu_limit must be a finite number > 0 or None, got {swiglu_limit!r}")
+    return float(swiglu_limit)
 
 
 def hip_fused_moe_forward(num_experts, routing_weights, selected_experts,
@@ -168,10 +214,12 @@ def hip_fused_moe_forward(num_experts, routing_weights, selected_experts,
                           fc1_1_2_weight=None, swiglu_limit=None):
     """Signature parity: group_gemm_fused_moe_forward (group_gemm.py:523-603).
 
-    Round-1 scope: merged fc1 only (the layout our models and the reference's
-    v5 experts use); swiglu_limit (gpt-oss clamp) is off-path."""
-    if swiglu_limit is not None:
-        raise NotImplementedError("swiglu_limit is off the §8 hot path")
+    Merged fc1 is the native layout (our models and the reference's v5
+    experts use it); split weights are concatenated and take the same path.
+    swiglu_limit (clamped SwiGLU: gate <= L, -L <= up <= L, gradients zeroed
+    outside) is validated here, before any device work, and handed to the
+    expert class; None keeps the unclamped kernels."""
+    swiglu_limit = check_swiglu_limit(swiglu_limit)
     if fc1_1_2_weight is None:
         if fc1_1_weight is None or fc1_2_weight is None:
             raise ValueError("need merged fc1_1_2_weight or both split weights")
@@ -181,13 +229,13 @@ def hip_fused_moe_forward(num_experts, routing_weights, selected_experts,
         from ...distributed.moe import dispatch_to_ep_a2a_class
 
         out = dispatch_to_ep_a2a_class(
-            EPMergedFc1HipGroupGemmA2A, num_experts, routing_weights,
+            ep_a2a_class_for_limit(swiglu_limit), num_experts, routing_weights,
             selected_experts, hs, fc1_1_2_weight, fc2_weight,
         )
     else:
         out = HipFusedMoeFunction.apply(
             num_experts, routing_weights, selected_experts, hs,
-            fc1_1_2_weight, fc2_weight,
+            fc1_1_2_weight, fc2_weight, swiglu_limit,
         )
     return out.reshape(hidden_states.shape)
 

@@ -63,53 +63,34 @@ int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
                           int64_t total_rows, int trans_b, int accumulate,
                           int activation, void* stream);
 
-/* Deep-pipelined 256x256 variant of vh_group_gemm_nk_bf16 (same semantics,
- * no accumulate/activation); auto-dispatched for large shapes, exported for
- * direct benchmarking. K % 32 == 0, K >= 64. */
+/* The three 256x256 kernels below are what vh_group_gemm_nk_bf16 /
+ * vh_group_gemm_mn_bf16 dispatch to for large shapes; they are exported for
+ * direct benchmarking. Everything else runs the 128x128 kernels. */
+
+/* Deep-pipelined 256x256 kernel for trans_b == 0 (B [G,K,N]), no
+ * accumulate/activation. vh_group_gemm_nk_bf16 dispatches to it for
+ * !trans_b, K % 32 == 0, K >= 1024, N >= 1024, total_rows >= 256*G.
+ * K % 32 == 0, K >= 64, N % 16 == 0. trans_b != 0 is an error (that layout
+ * is served by nk256s). */
 int vh_group_gemm_nk8_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
                            const int64_t* cumsum, int G, int64_t N, int64_t K,
                            int64_t total_rows, int trans_b, void* stream);
 
-/* 256-square double-buffered glds variant (trans_b semantics; K % 64 == 0);
- * kept for A/B benchmarking — the dispatched fast path is nk256s below. */
-int vh_group_gemm_nk256_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
-                             const int64_t* cumsum, int G, int64_t N,
-                             int64_t K, int64_t total_rows, void* stream);
-
-/* nk256 inner loop under a device-built tile schedule with XCD-clustered
- * persistent blocks (L2 reuse of the per-group A/B tiles; no skew-sized
- * null-block grid). The dispatched trans_b fast path. G <= 4096. NOTE: on
- * first use this entry hipMallocs one small (~16 KB) schedule workspace
- * that lives for the process (the single exception to the no-allocation
- * convention; calls on one stream serialize on it). */
+/* 256-square double-buffered glds kernel (trans_b semantics, B [G,N,K])
+ * under a device-built tile schedule with XCD-clustered persistent blocks
+ * (L2 reuse of the per-group A/B tiles; no skew-sized null-block grid).
+ * vh_group_gemm_nk_bf16 dispatches to it for trans_b, K % 64 == 0,
+ * N >= 256, total_rows >= 256*G, G <= 4096. NOTE: on first use this entry
+ * hipMallocs one small (~16 KB) schedule workspace that lives for the
+ * process (the single exception to the no-allocation convention; calls on
+ * one stream serialize on it). */
 int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
                               uint16_t* C, const int64_t* cumsum, int G,
                               int64_t N, int64_t K, int64_t total_rows,
                               void* stream);
 
-/* probe: nk256s with the 32x32x16 MFMA inner loop (issue-stall attack). */
-int vh_group_gemm_nk256s32_bf16(const uint16_t* A, const uint16_t* B,
-                                uint16_t* C, const int64_t* cumsum, int G,
-                                int64_t N, int64_t K, int64_t total_rows,
-                                void* stream);
-
-/* Probe kernels kept for on-box A/B (trans_b semantics, XCD schedule):
- * nk8s = KSUB=32 counted-vmcnt 4-deep ring; nkp = 8-phase K-split pipeline
- * reconstruction. Both race-screened correct; neither dispatched (measured
- * slower than nk256s — see profiles/r02_groupgemm_pmc.txt / DESIGN.md). */
-int vh_group_gemm_nk8s_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
-                            const int64_t* cumsum, int G, int64_t N,
-                            int64_t K, int64_t total_rows, void* stream);
-int vh_group_gemm_nkp_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
-                           const int64_t* cumsum, int G, int64_t N, int64_t K,
-                           int64_t total_rows, void* stream);
-
-/* Register-staged 256-square ring variants (auto-dispatched):
- * dgrad8 = !trans_b semantics; mn8 = wgrad (A^T B) semantics. */
-int vh_group_gemm_dgrad8_bf16(const uint16_t* A, const uint16_t* B,
-                              uint16_t* C, const int64_t* cumsum, int G,
-                              int64_t N, int64_t K, int64_t total_rows,
-                              void* stream);
+/* Register-staged 256-square ring kernel with wgrad (A^T B) semantics;
+ * vh_group_gemm_mn_bf16 dispatches to it for M >= 1024 and N >= 1024. */
 int vh_group_gemm_mn8_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
                            const int64_t* cumsum, int G, int64_t M, int64_t N,
                            void* stream);
@@ -250,19 +231,12 @@ int vh_attn_bwd_pre_bf16(const uint16_t* dO, const uint16_t* O,
                          const float* LSE, float* delta, float* lse2,
                          int64_t rows, void* stream);
 
-/* Backward (monolithic PROBE variant): dQacc [B,Hq,S,128] fp32 (caller
- * zero-fills; atomically accumulated), dK/dV [B,Hq,S,128] bf16 per Q-head
- * (caller sums GQA groups). delta/lse2 from the preprocess. */
-int vh_attn_bwd_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
-                     const uint16_t* dO, const float* delta, const float* lse2,
-                     float* dQacc, uint16_t* dK, uint16_t* dV, int B, int Hq,
-                     int Hkv, int64_t S, float scale, void* stream);
-
-/* Split backward (the dispatched path): GQA-folded dk/dv kernel (block owns
- * 128 kv rows of one KV head and loops the whole Hq/Hkv head group — dK/dV
- * are [B,Hkv,S,128] bf16 written once, no per-Q-head intermediates) + dq
- * kernel (block owns 128 q rows, dQ [B,Hq,S,128] bf16 written once — no
- * atomics, no fp32 accumulator). doc_start/doc_end (nullable together,
+/* Backward: GQA-folded dk/dv kernel (block owns a 64-row kv strip of one KV
+ * head and loops the whole Hq/Hkv head group — dK/dV are [B,Hkv,S,128] bf16
+ * written once, no per-Q-head intermediates) + dq kernel (block owns 128 q
+ * rows, dQ [B,Hq,S,128] bf16 written once — no atomics, no fp32
+ * accumulator). delta/lse2 from the preprocess; S % 128 == 0.
+ * doc_start/doc_end (nullable together,
  * require B == 1): int32 [S] per-token document bounds for the packed-varlen
  * block-diagonal causal mask (see vh_attn_fwd_bf16). */
 int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,

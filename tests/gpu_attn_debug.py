@@ -6,7 +6,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-import ctypes
 import math
 import time
 
@@ -118,53 +117,6 @@ def main():
     flb = 3 * 2 * 2 * S * S * Hq * 128 * 0.5
     print(f"bwd llama shape: {dt*1e3:.3f} ms  {flb/dt/1e12:.0f} TF/s", flush=True)
 
-    # A/B: round-1 per-Q-head dkv (v2 probe) vs the GQA-folded v5 in the path
-    lib = L.get_lib()
-    fn2 = lib.vh_attn_bwd2_dkv2probe_bf16
-    fn2.restype = ctypes.c_int
-    fn2.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 3 + [
-        ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]
-    rows = B * Hq * S
-    delta = torch.zeros(rows, dtype=torch.float32, device=dev)
-    lse2 = (lse.flatten() * 1.4426950408889634).contiguous()
-    dkh = torch.empty(B, Hq, S, 128, dtype=torch.bfloat16, device=dev)
-    dvh = torch.empty(B, Hq, S, 128, dtype=torch.bfloat16, device=dev)
-    for _ in range(3):
-        fn2(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-            delta.data_ptr(), lse2.data_ptr(), dkh.data_ptr(), dvh.data_ptr(),
-            B, Hq, Hkv, S, scale, L.cur_stream())
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(10):
-        fn2(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-            delta.data_ptr(), lse2.data_ptr(), dkh.data_ptr(), dvh.data_ptr(),
-            B, Hq, Hkv, S, scale, L.cur_stream())
-    torch.cuda.synchronize()
-    dt2p = (time.perf_counter() - t0) / 10
-    print(f"dkv v2 probe (per-Q-head): {dt2p*1e3:.3f} ms", flush=True)
-
-    # dkv v6 prefetch-depth A/B (PREF = 0 / 4 / 8)
-    fn6 = lib.vh_attn_bwd2_dkv6probe_bf16
-    fn6.restype = ctypes.c_int
-    fn6.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 3 + [
-        ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
-    dkv = torch.empty(B, Hkv, S, 128, dtype=torch.bfloat16, device=dev)
-    dvv = torch.empty(B, Hkv, S, 128, dtype=torch.bfloat16, device=dev)
-    for pref in (0, 4, 8):
-        for _ in range(3):
-            fn6(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-                delta.data_ptr(), lse2.data_ptr(), dkv.data_ptr(), dvv.data_ptr(),
-                B, Hq, Hkv, S, scale, pref, L.cur_stream())
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(10):
-            fn6(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-                delta.data_ptr(), lse2.data_ptr(), dkv.data_ptr(), dvv.data_ptr(),
-                B, Hq, Hkv, S, scale, pref, L.cur_stream())
-        torch.cuda.synchronize()
-        dt6 = (time.perf_counter() - t0) / 10
-        print(f"dkv v6 pref={pref}: {dt6*1e3:.3f} ms", flush=True)
-
     # AOTriton reference: time the torch SDPA backward at the same shape
     qf = q.clone().requires_grad_(True)
     kf = k.clone().requires_grad_(True)
@@ -217,80 +169,3 @@ def main():
 
 if __name__ == "__main__":
     main()
-
-
-def probe():
-    import ctypes
-    lib = L.get_lib()
-    fn = lib.vh_attn_fwd_probe_bf16
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
-    dev = "cuda"
-    B, Hq, Hkv, S = 1, 32, 8, 4096
-    import math
-    scale = 1.0 / math.sqrt(128)
-    q = (torch.randn(B, Hq, S, 128, device=dev) * 0.5).to(torch.bfloat16)
-    k = (torch.randn(B, Hkv, S, 128, device=dev) * 0.5).to(torch.bfloat16)
-    v = (torch.randn(B, Hkv, S, 128, device=dev) * 0.5).to(torch.bfloat16)
-    o = torch.empty_like(q)
-    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=dev)
-    fl = 2 * 2 * S * S * Hq * 128 * 0.5
-    for mode, name in [(0, "full"), (1, "no-softmax"), (2, "no-PV"), (3, "no-QK")]:
-        for _ in range(3):
-            fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
-               B, Hq, Hkv, S, scale, mode, L.cur_stream())
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(10):
-            fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(),
-               B, Hq, Hkv, S, scale, mode, L.cur_stream())
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 10
-        print(f"probe {name}: {dt*1e3:.3f} ms ({fl/dt/1e12:.0f} TF/s-equiv)", flush=True)
-
-
-if os.environ.get("VH_ATTN_PROBE"):
-    probe()
-
-
-def probe_bwd():
-    import ctypes
-    lib = L.get_lib()
-    fn = lib.vh_attn_bwd_probe_bf16
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
-    dev = "cuda"
-    B, Hq, Hkv, S = 1, 32, 8, 4096
-    scale = 1.0 / math.sqrt(128)
-    q = (torch.randn(B, Hq, S, 128, device=dev) * 0.5).to(torch.bfloat16)
-    k = (torch.randn(B, Hkv, S, 128, device=dev) * 0.5).to(torch.bfloat16)
-    v = (torch.randn(B, Hkv, S, 128, device=dev) * 0.5).to(torch.bfloat16)
-    do = torch.randn_like(q)
-    o, lse = attn_fwd(q, k, v, scale)
-    rows = B * Hq * S
-    delta = torch.zeros(rows, dtype=torch.float32, device=dev)
-    lse2 = lse.flatten() * 1.4426950408889634
-    dqacc = torch.zeros(B, Hq, S, 128, dtype=torch.float32, device=dev)
-    dk = torch.empty(B, Hq, S, 128, dtype=torch.bfloat16, device=dev)
-    dv = torch.empty(B, Hq, S, 128, dtype=torch.bfloat16, device=dev)
-    flb = 3 * 2 * 2 * S * S * Hq * 128 * 0.5
-    names = {0: "full", 1: "no-dQ", 2: "no-phase2(dV/dK)", 3: "no-softmax", 4: "no-qt-staging", 5: "no-qrow-loads", 6: "no-global-flush", 7: "no-lds-dsadd", 8: "no-dq-mfma"}
-    for mode in [0, 1, 2, 3, 4, 5, 6, 7, 8]:
-        for _ in range(2):
-            rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-                    delta.data_ptr(), lse2.data_ptr(), dqacc.data_ptr(),
-                    dk.data_ptr(), dv.data_ptr(), B, Hq, Hkv, S, scale, mode, L.cur_stream())
-            assert rc == 0, lib.vh_last_error()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(5):
-            fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), do.data_ptr(),
-               delta.data_ptr(), lse2.data_ptr(), dqacc.data_ptr(),
-               dk.data_ptr(), dv.data_ptr(), B, Hq, Hkv, S, scale, mode, L.cur_stream())
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 5
-        print(f"bwd probe {names[mode]}: {dt*1e3:.3f} ms ({flb/dt/1e12:.0f} TF/s-equiv)", flush=True)
-
-
-if os.environ.get("VH_ATTN_PROBE_BWD"):
-    probe_bwd()

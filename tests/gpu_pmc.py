@@ -32,15 +32,15 @@ def main():
     cw = torch.empty(E, 2 * I, H, dtype=torch.bfloat16, device=dev)
     s = L.cur_stream()
     for _ in range(5):
-        # fwd on nk256 (current dispatch target)
-        lib.vh_group_gemm_nk256_bf16(a.data_ptr(), w1.data_ptr(), c1.data_ptr(),
-                                     cumsum.data_ptr(), E, 2 * I, H, rows, s)
+        # fwd on nk256s (current dispatch target)
+        lib.vh_group_gemm_nk256s_bf16(a.data_ptr(), w1.data_ptr(), c1.data_ptr(),
+                                      cumsum.data_ptr(), E, 2 * I, H, rows, s)
         # fc1 dgrad on nk8 (current dispatch target)
         lib.vh_group_gemm_nk8_bf16(g1.data_ptr(), w1.data_ptr(), c2.data_ptr(),
                                    cumsum.data_ptr(), E, H, 2 * I, rows, 0, s)
-        # wgrad on mn8 (current dispatch target)
-        lib.vh_group_gemm_mn8_bf16(g1.data_ptr(), a.data_ptr(), cw.data_ptr(),
-                                   cumsum.data_ptr(), E, 2 * I, H, s)
+        # wgrad on mn8 (what vh_group_gemm_mn_bf16 dispatches to at M, N >= 1024)
+        lib.vh_group_gemm_mn_bf16(g1.data_ptr(), a.data_ptr(), cw.data_ptr(),
+                                  cumsum.data_ptr(), E, 2 * I, H, s)
     torch.cuda.synchronize()
     print("pmc probe done")
 

@@ -296,8 +296,11 @@ def test_fused_moe_fwd_bwd_vs_eager_gpu(lib):
 
 
 def test_group_gemm_nk8_ragged(lib):
-    """Exercises the 256x256 8-phase kernel (auto-dispatch at large rows),
-    K%32 (not 64), empty group, ragged tails, both B layouts."""
+    """Large-rows dispatch with an empty group and ragged tails, both B
+    layouts. K = 96 is zero-padded to 128 by hip_lib, so the trans_b shapes
+    (N 288 / K 128 and N 256 / K 2048) reach the persistent 256x256 nk256s
+    kernel and the !trans_b shape (K < 1024) the 128x128 kernel. The 8-phase
+    nk8 kernel is covered by test_group_gemm_nk8_notransb_wide."""
     torch.manual_seed(12)
     counts = [500, 0, 279, 333]
     G, rows = len(counts), sum(counts)
@@ -315,6 +318,30 @@ def test_group_gemm_nk8_ragged(lib):
             torch.testing.assert_close(c[start:end].float(), ref, rtol=3e-2, atol=3e-2,
                                        msg=lambda m: f"g={g} trans_b={trans_b} N={N} K={K}: {m}")
             start = end
+
+
+def test_group_gemm_nk8_notransb_wide(lib):
+    """!trans_b with K, N >= 1024 and rows >= 256*G is the one dispatch that
+    reaches the 256x256 8-phase nk8 kernel: empty group, ragged tails, N a
+    16-multiple but not a 256-multiple (partial last n-tile). Reference:
+    per-group fp32 matmul on the device."""
+    torch.manual_seed(14)
+    counts = [500, 0, 279, 333]
+    G, rows = len(counts), sum(counts)
+    N, K = 1040, 1024
+    cumsum = torch.tensor(counts).cumsum(0).cuda()
+    a = bf(torch.randn(rows, K) * 0.5).cuda()
+    b = bf(torch.randn(G, K, N) * 0.5).cuda()
+    c = lib.group_gemm_nk(a, b, cumsum, trans_b=False)
+    start = 0
+    for g in range(G):
+        end = int(cumsum[g])
+        if end == start:
+            continue
+        ref = a[start:end].float() @ b[g].float()
+        torch.testing.assert_close(c[start:end].float(), ref, rtol=3e-2, atol=3e-2,
+                                   msg=lambda m: f"g={g}: {m}")
+        start = end
 
 
 def test_group_gemm_wgrad_transpose_path(lib):

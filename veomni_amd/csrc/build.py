@@ -30,7 +30,9 @@ SOURCES = [
 
 def build(verbose: bool = True) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    newest_src = max(os.path.getmtime(s) for s in srcs + [os.path.join(CSRC, "vh_common.h")])
+    headers = [os.path.join(CSRC, "vh_common.h"),
+               os.path.join(os.path.dirname(PKG), "include", "veomni_hip.h")]
+    newest_src = max(os.path.getmtime(s) for s in srcs + headers)
     if os.path.exists(OUT) and os.path.getmtime(OUT) > newest_src:
         if verbose:
             print(f"[vh build] up to date: {OUT}")

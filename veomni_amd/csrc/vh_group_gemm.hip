@@ -24,6 +24,7 @@
 //     __syncthreads per K-step (guide T3 "minimum 2-phase" recipe).
 
 #include "vh_common.h"
+#include "../../include/veomni_hip.h"  // the 256x256 entries dispatched to
 
 namespace {
 
@@ -352,28 +353,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_group_gemm_mn(
 
 }  // namespace
 
-extern "C" int vh_group_gemm_nk256_bf16(const uint16_t* A, const uint16_t* B,
-                                        uint16_t* C, const int64_t* cumsum,
-                                        int G, int64_t N, int64_t K,
-                                        int64_t total_rows, void* stream);
-extern "C" int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
-                                         uint16_t* C, const int64_t* cumsum,
-                                         int G, int64_t N, int64_t K,
-                                         int64_t total_rows, void* stream);
-extern "C" int vh_group_gemm_nk8_bf16(const uint16_t* A, const uint16_t* B,
-                                      uint16_t* C, const int64_t* cumsum,
-                                      int G, int64_t N, int64_t K,
-                                      int64_t total_rows, int trans_b,
-                                      void* stream);
-extern "C" int vh_group_gemm_dgrad8_bf16(const uint16_t* A, const uint16_t* B,
-                                         uint16_t* C, const int64_t* cumsum,
-                                         int G, int64_t N, int64_t K,
-                                         int64_t total_rows, void* stream);
-extern "C" int vh_group_gemm_mn8_bf16(const uint16_t* A, const uint16_t* B,
-                                      uint16_t* C, const int64_t* cumsum,
-                                      int G, int64_t M, int64_t N,
-                                      void* stream);
-
 extern "C" int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B,
                                      uint16_t* C, const int64_t* cumsum, int G,
                                      int64_t N, int64_t K, int64_t total_rows,
@@ -381,8 +360,9 @@ extern "C" int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B,
                                      int activation, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // Per-shape dispatch from measured data (profiles/r01_groupgemm_microbench):
-  //   trans_b large   -> nk256 (256-sq double-buffered glds; fastest fwd)
-  //   !trans_b wide   -> nk8   (glds A + transposed B ring)
+  //   trans_b large   -> nk256s (256-sq double-buffered glds, persistent
+  //                      XCD-clustered schedule; fastest fwd)
+  //   !trans_b wide   -> nk8    (glds A + transposed B ring)
   //   everything else -> the 128x128 2-phase kernel
   if (!accumulate && activation == 0 && trans_b && K % 64 == 0 && N >= 256 &&
       total_rows >= (int64_t)G * 256 && G <= 4096) {

@@ -50,13 +50,7 @@ def get_lib() -> ctypes.CDLL:
          c_i64, c_int, c_int, c_int, c_p)
     _sig(lib, "vh_group_gemm_nk8_bf16", c_p, c_p, c_p, c_p, c_int, c_i64, c_i64,
          c_i64, c_int, c_p)
-    _sig(lib, "vh_group_gemm_nk256_bf16", c_p, c_p, c_p, c_p, c_int, c_i64,
-         c_i64, c_i64, c_p)
     _sig(lib, "vh_group_gemm_nk256s_bf16", c_p, c_p, c_p, c_p, c_int, c_i64,
-         c_i64, c_i64, c_p)
-    _sig(lib, "vh_group_gemm_nk8s_bf16", c_p, c_p, c_p, c_p, c_int, c_i64,
-         c_i64, c_i64, c_p)
-    _sig(lib, "vh_group_gemm_nkp_bf16", c_p, c_p, c_p, c_p, c_int, c_i64,
          c_i64, c_i64, c_p)
     _sig(lib, "vh_group_gemm_mn_bf16", c_p, c_p, c_p, c_p, c_int, c_i64, c_i64, c_p)
     _sig(lib, "vh_transpose_pad_bf16", c_p, c_p, c_p, c_p, c_int, c_i64, c_i64, c_p)
@@ -82,8 +76,6 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_attn_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int,
          c_i64, c_f32, c_p, c_p)
     _sig(lib, "vh_attn_bwd_pre_bf16", c_p, c_p, c_p, c_p, c_p, c_i64, c_p)
-    _sig(lib, "vh_attn_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-         c_int, c_int, c_int, c_i64, c_f32, c_p)
     _sig(lib, "vh_attn_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_fwd", c_p, c_int, c_p, c_i64, c_int, c_int, c_p, c_int, c_p)

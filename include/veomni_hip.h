@@ -63,13 +63,14 @@ int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
                           int64_t total_rows, int trans_b, int accumulate,
                           int activation, void* stream);
 
-/* The three 256x256 kernels below are what vh_group_gemm_nk_bf16 /
+/* The 256x256 kernels below are what vh_group_gemm_nk_bf16 /
  * vh_group_gemm_mn_bf16 dispatch to for large shapes; they are exported for
  * direct benchmarking. Everything else runs the 128x128 kernels. */
 
 /* Deep-pipelined 256x256 kernel for trans_b == 0 (B [G,K,N]), no
  * accumulate/activation. vh_group_gemm_nk_bf16 dispatches to it for
- * !trans_b, K % 32 == 0, K >= 1024, N >= 1024, total_rows >= 256*G.
+ * !trans_b, K % 32 == 0, K >= 1024, N >= 1024, total_rows >= 256*G where
+ * nk256s_kn does not apply (K % 64 == 32 or G > 4096).
  * K % 32 == 0, K >= 64, N % 16 == 0. trans_b != 0 is an error (that layout
  * is served by nk256s). */
 int vh_group_gemm_nk8_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
@@ -88,6 +89,17 @@ int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
                               uint16_t* C, const int64_t* cumsum, int G,
                               int64_t N, int64_t K, int64_t total_rows,
                               void* stream);
+
+/* The same kernel for trans_b == 0 (B [G,K,N] as stored — dgrad straight
+ * from the expert weights, no transposed copy): the B tile is staged
+ * [64 k][256 n] and its MFMA fragments are read with transposing LDS reads.
+ * Same constraints, dispatch conditions and schedule workspace as above;
+ * feeds the MFMAs the operands vh_group_gemm_nk256s_bf16 would get from
+ * the transposed weights, in the same order (bit-equal results). */
+int vh_group_gemm_nk256s_kn_bf16(const uint16_t* A, const uint16_t* B,
+                                 uint16_t* C, const int64_t* cumsum, int G,
+                                 int64_t N, int64_t K, int64_t total_rows,
+                                 void* stream);
 
 /* Register-staged 256-square ring kernel with wgrad (A^T B) semantics;
  * vh_group_gemm_mn_bf16 dispatches to it for M >= 1024 and N >= 1024. */
@@ -109,18 +121,16 @@ int vh_group_gemm_mn_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
 int vh_wtranspose_bf16(const uint16_t* src, uint16_t* dst, int E, int64_t M,
                        int64_t N, void* stream);
 
-/* Transpose-pad: [rows, C] (rows grouped by cumsum) -> [C, padded_total]
- * with each group's rows zero-padded to a 64-multiple (padded_cumsum,
- * host-computed ceil64 cumsum). Regions past the last group are untouched. */
-int vh_transpose_pad_bf16(const uint16_t* src, uint16_t* dst,
-                          const int64_t* cumsum, const int64_t* padded_cumsum,
-                          int G, int64_t C, int64_t padded_total, void* stream);
-
-/* wgrad over transpose-padded operands: C[g] = A'[:, pg] @ B'[:, pg]^T,
- * A' [M, PR], B' [N, PR]; group g owns padded-row range pg (64-multiples). */
-int vh_group_gemm_wg256_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
-                             const int64_t* padded_cumsum, int G, int64_t M,
-                             int64_t N, int64_t PR, void* stream);
+/* Direct wgrad for large shapes: C[g] (M x N) = A_g^T @ B_g with A [rows, M]
+ * and B [rows, N] token-major as autograd hands them over (no transposed or
+ * padded copies, no temporaries); group g owns rows [cumsum[g-1], cumsum[g])
+ * at any alignment. 256x256 tiles, persistent XCD-clustered schedule, both
+ * operands staged [64 k][256 out] and read with transposing LDS reads. Rows
+ * outside a group never contribute (the last k-tile's tail is zeroed in
+ * LDS), zero-count groups are zero-filled. M % 16 == 0, N % 16 == 0. */
+int vh_group_gemm_wgd_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
+                           const int64_t* cumsum, int G, int64_t M, int64_t N,
+                           int64_t total_rows, void* stream);
 
 /* ---- Fused MoE elementwise --------------------------------------------- */
 

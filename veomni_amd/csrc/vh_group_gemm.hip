@@ -359,17 +359,22 @@ extern "C" int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B,
                                      int trans_b, int accumulate,
                                      int activation, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // Per-shape dispatch from measured data (profiles/r01_groupgemm_microbench):
-  //   trans_b large   -> nk256s (256-sq double-buffered glds, persistent
-  //                      XCD-clustered schedule; fastest fwd)
-  //   !trans_b wide   -> nk8    (glds A + transposed B ring)
+  // Per-shape dispatch from measured data (profiles/r01_groupgemm_microbench,
+  // profiles/gg_direct_operands_ab.md):
+  //   large, either B layout -> nk256s (256-sq double-buffered glds, persistent
+  //                      XCD-clustered schedule; B [G,K,N] is staged as it is
+  //                      stored and read with transposing LDS reads)
+  //   !trans_b wide, K % 64 == 32 or G > 4096 -> nk8 (glds A + transposed B ring)
   //   everything else -> the 128x128 2-phase kernel
-  if (!accumulate && activation == 0 && trans_b && K % 64 == 0 && N >= 256 &&
+  if (!accumulate && activation == 0 && K % 64 == 0 && N >= 256 &&
       total_rows >= (int64_t)G * 256 && G <= 4096) {
     // nk256s: device-built tile schedule + XCD-clustered persistent blocks
     // (L2 reuse; no skew-sized null-block grid) — see vh_group_gemm8.hip
-    return vh_group_gemm_nk256s_bf16(A, B, C, cumsum, G, N, K, total_rows,
-                                     stream);
+    if (trans_b)
+      return vh_group_gemm_nk256s_bf16(A, B, C, cumsum, G, N, K, total_rows,
+                                       stream);
+    return vh_group_gemm_nk256s_kn_bf16(A, B, C, cumsum, G, N, K, total_rows,
+                                        stream);
   }
   if (!accumulate && activation == 0 && !trans_b && K % 32 == 0 && K >= 1024 &&
       N >= 1024 && total_rows >= 16 * G * 16) {

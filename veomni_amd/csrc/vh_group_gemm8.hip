@@ -1,7 +1,8 @@
 // 256x256 grouped GEMMs for gfx950 (bf16, fp32 accumulate): the 8-phase
-// nk8 (below), the register-staged mn8 ring, the persistent XCD-scheduled
-// nk256s / wg256s and the transpose-pad kernel. Retired variants are at
-// commit 49b7734; what they measured is in DESIGN.md.
+// nk8 (below), the register-staged mn8 ring and the persistent XCD-scheduled
+// nk256s (fwd, and dgrad straight from the stored weights) / wgd256s (wgrad
+// straight from the token-major operands). Retired variants are at commits
+// 49b7734 and 2f18dcb; what they measured is in DESIGN.md.
 //
 // nk8: the deep-pipelined variant of vh_group_gemm.hip's same-NK kernel, built on
 // the guide's 256-square 8-phase recipe (cdna_hip_programming.md §5 "The 256²
@@ -19,10 +20,13 @@
 //   each k-sub for slot s+3; vmcnt(6) then admits slot s while 3 slots stay
 //   in flight.
 //
-// Dispatched by vh_group_gemm_nk_bf16 (vh_group_gemm.hip) for large shapes
-// with B [K, N] (!trans_b).
+// Dispatched by vh_group_gemm_nk_bf16 (vh_group_gemm.hip) for the large
+// B [K, N] (!trans_b) shapes that nk256s_kn does not take (K % 64 == 32,
+// G > 4096).
 
 #include "vh_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -477,7 +481,7 @@ extern "C" int vh_group_gemm_mn8_bf16(const uint16_t* A, const uint16_t* B,
 
 // ============================================================================
 // 256x256 x BK=64 double-buffered glds structure (shared by nk256s and
-// wg256s below): the 128x128 2-phase structure scaled to a 256-square tile —
+// wgd256s below): the 128x128 2-phase structure scaled to a 256-square tile —
 // 2x the MFMA work per staged byte and per barrier drain, with the proven
 // conflict-free 128-B-row swizzle.
 // 8 waves (2x4), per wave 128x64; LDS = 2 x (A 32K + B 32K) = 128 KiB.
@@ -527,6 +531,136 @@ __device__ __forceinline__ bf16frag frag_read64(const bf16_t* tile, int row0,
       reinterpret_cast<const char*>(tile) + off_b);
 }
 
+// ----------------------------------------------------------------------------
+// "Reduction-slow" tiles: a [64 k][256 out] bf16 tile (32 KiB, the footprint
+// of the [256][64] tile above) of an operand whose reduction index is the
+// SLOW one in memory — both wgrad operands ([rows, M] / [rows, N], k = row)
+// and the stored weights W[g][K][N] for dgrad. No transposed copy is made:
+// the tile is staged as it lies in memory and the MFMA fragments are read
+// with the CDNA4 transposing LDS read (ds_read_b64_tr_b16).
+//
+// Image: k-row r occupies bytes [512 r, 512 r + 512); inside the row the
+// sixteen 32-B segments (16 outs each) are permuted,
+//     off(r, seg) = 512 r + 32 (seg ^ h(r)),   h(r) = (r & 3) | ((r >> 3) & 1) << 2.
+// Why this h. A transposed read hands each 16-lane group a block of 4 k-rows
+// x 16 outs (lane 4q+p: row q, outs 4p..4p+3, 8 B). For the 16x16x32 operand,
+// group g of the wave takes k = 32 ks + 8 g + {0..3} (first read) and
+// + {4..7} (second read), all groups in the same 16 outs, i.e. the same seg.
+// Banks are counted per 32-lane half, 64 banks = 256 B: a half holds groups
+// {0,1} or {2,3}, so 8 k-rows {b..b+3} u {b+8..b+11} with b % 4 == 0, each
+// contributing one 32-B segment (8 banks). Rows are 512 B = 2 bank rows, so
+// without the XOR all 8 land on the same 8 banks (8-way). Over those 8 rows
+// r & 3 takes 0..3 and bit 3 of r takes both values, so h(r) takes all of
+// 0..7 and (seg ^ h) & 7 — the segment's 32-B position in the bank row — is
+// distinct for the 8 rows: 8 x 8 banks = all 64, conflict-free. h ignores
+// bit 2, so the second read (+4 rows) is the first one 2048 B further on.
+// Every lane address is 512 r + 32 x + 8 p: 8-byte aligned.
+// Fill: glds writes LDS lane-linearly (wave w, instruction i, lane l -> byte
+// 8192 i + 1024 w + 16 l: always conflict-free); the permutation is carried
+// by the per-lane SOURCE column, and since h(16 i + 2 w + (l >> 5)) does not
+// depend on i, one column offset per lane serves all four instructions. A
+// wave instruction fetches two whole 512-B k-rows: fully coalesced.
+// The transposed reads need EXEC all ones (the gather crosses lanes): they
+// are only ever issued from wave-uniform control flow; tails are handled by
+// padding the tile (clamped source row, zeroed LDS rows), never by masking.
+// ----------------------------------------------------------------------------
+__device__ __forceinline__ int tswz64(int k) {
+  return (k & 3) | (((k >> 3) & 1) << 2);
+}
+
+struct TStage64 {  // [64 k][256 out] tile via 4 glds of 8 KiB (512 threads)
+  const bf16_t* src;  // operand base + this lane's (permuted) column
+  int64_t ld;
+  int krow;           // this lane's k-row within each 16-row glds: 2 w + (l >> 5)
+  int wave;           // wave-uniform (SGPR)
+
+  // col_of(c): source column of tile column c (c a 16-multiple; wrap/clamp
+  // partial tiles there so every staged address stays in bounds)
+  template <typename ColFn>
+  __device__ __forceinline__ void init(const bf16_t* s, int64_t ld_elems,
+                                       ColFn col_of, int tid) {
+    const int lane = tid & 63;
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    krow = wave * 2 + (lane >> 5);
+    const int pb = (lane & 31) * 16;  // byte within the 512-B LDS row
+    const int seg = (pb >> 5) ^ tswz64(krow);
+    src = s + col_of(seg * 16) + ((pb & 31) >> 1);
+    ld = ld_elems;
+  }
+
+  // row_of(k): source row of tile k-row k0 + k' (a functor, so a row-index
+  // indirection can be folded in later)
+  template <typename RowFn>
+  __device__ __forceinline__ void stage(bf16_t* tile, int k0, RowFn row_of) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      glds16(src + (int64_t)row_of(k0 + i * 16 + krow) * ld,
+             tile + ((i * 8192 + wave * 1024) >> 1));
+  }
+
+  // Zero the k-rows >= rem that THIS wave staged (call after vmcnt(0), before
+  // the barrier that publishes the tile). Wave-uniform branches; a row is
+  // one 64-lane x 8-B store.
+  __device__ __forceinline__ void zero_tail(bf16_t* tile, int rem, int lane) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int k = i * 16 + wave * 2 + b;
+        if (k >= rem)
+          *reinterpret_cast<uint2*>(reinterpret_cast<char*>(tile) + k * 512 +
+                                    lane * 8) = uint2{0u, 0u};
+      }
+  }
+};
+
+// 16x16x32 fragments (out = out0 + (lane & 15), k = 32 ks + 8 (lane >> 4) +
+// 0..7: the k-to-lane map of frag_read64) from a [64 k][256 out] tile, as two
+// transposed reads of 4 k each.
+// The reads are inline asm on purpose: through the builtin the compiler
+// cannot tell them from the tile the LDS-DMA is filling and puts
+// s_waitcnt vmcnt(0) in front of the first read, which serialises the
+// prefetch of the next k-tile with the MFMAs of this one. The asm is opaque
+// to the compiler's counters, so tr_wait ties the destination registers to
+// an explicit s_waitcnt lgkmcnt(0): nothing can use (or copy) them earlier.
+using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+struct TrFrag { u32x2 lo, hi; };
+
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p;
+}
+
+// this lane's byte offset in the tile for the fragment at outs out0..out0+15
+__device__ __forceinline__ int tr_lane_off(int out0, int lane) {
+  const int k = ((lane >> 4) << 3) + ((lane >> 2) & 3);
+  return k * 512 + (((out0 >> 4) ^ tswz64(k)) << 5) + (lane & 3) * 8;
+}
+
+// addr = LDS byte address of the tile + tr_lane_off; KS = 32-k half (0/1)
+template <int KS>
+__device__ __forceinline__ void tr_issue(TrFrag& f, uint32_t addr) {
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %2 offset:%3\n\t"
+      "ds_read_b64_tr_b16 %1, %2 offset:%4"
+      : "=&v"(f.lo), "=&v"(f.hi)
+      : "v"(addr), "n"(KS * 16384), "n"(KS * 16384 + 2048)
+      : "memory");
+}
+
+__device__ __forceinline__ void tr_wait(TrFrag (&f)[4]) {
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi),
+                 "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo), "+v"(f[3].hi)
+               :
+               : "memory");
+}
+
+__device__ __forceinline__ bf16frag tr_frag(const TrFrag& f) {
+  u32x4 u{f.lo.x, f.lo.y, f.hi.x, f.hi.y};
+  return __builtin_bit_cast(bf16frag, u);
+}
+
 // ============================================================================
 // nk256s: the inner loop above under a DEVICE-BUILT tile schedule with
 // XCD-clustered persistent blocks.
@@ -569,6 +703,12 @@ __global__ void k_gg_sched(const int64_t* __restrict__ cumsum, int G,
   }
 }
 
+// BKN = false: B [G, N, K] (trans_b), staged K-contiguous like A.
+// BKN = true:  B [G, K, N] as stored (dgrad straight from the weights): the
+// B tile is a "reduction-slow" [64 k][256 n] tile (TStage64 / tr_issue).
+// The k-to-lane map of the fragments is the same in both, so both feed the
+// MFMAs identical operands in identical order.
+template <bool BKN>
 __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
     bf16_t* __restrict__ C, const int64_t* __restrict__ cumsum, int G,
@@ -611,14 +751,28 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
     bf16_t* Cg = C + row_start * N;
 
     KStage64 sa, sb;
+    TStage64 sbt;
     sa.init(Ag, K, [&](int r) -> int64_t {
       int64_t gm = (int64_t)bm * BM8 + r;
       return gm % m_size;
     }, tid);
-    sb.init(Bg, K, [&](int r) -> int64_t {
-      int64_t gn = (int64_t)bn * BN8 + r;
-      return gn % N;
-    }, tid);
+    if constexpr (BKN) {
+      sbt.init(Bg, N, [&](int c) -> int64_t {
+        return ((int64_t)bn * BN8 + c) % N;
+      }, tid);
+    } else {
+      sb.init(Bg, K, [&](int r) -> int64_t {
+        int64_t gn = (int64_t)bn * BN8 + r;
+        return gn % N;
+      }, tid);
+    }
+    auto stage_b = [&](bf16_t* tile, int kt) {
+      if constexpr (BKN) sbt.stage(tile, kt * BK64, [](int k) { return k; });
+      else sb.stage(tile, (int64_t)kt * BK64);
+    };
+    int btr_off[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) btr_off[j] = tr_lane_off(wc * 64 + j * 16, lane);
 
     f32x4 acc[8][4];
 #pragma unroll
@@ -627,14 +781,50 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
       for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
     sa.stage(ta(0), 0);
-    sb.stage(tb(0), 0);
+    stage_b(tb(0), 0);
+    if constexpr (BKN) VMCNT(0);
     __syncthreads();
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
       if (kt + 1 < nk) {
         sa.stage(ta(cur ^ 1), (int64_t)(kt + 1) * BK64);
-        sb.stage(tb(cur ^ 1), (int64_t)(kt + 1) * BK64);
+        stage_b(tb(cur ^ 1), kt + 1);
       }
+      // fragments of one 32-k half; the MFMA clusters are the same for both
+      // B layouts
+      auto ks_step = [&](auto ks_c) {
+        constexpr int ks = decltype(ks_c)::value;
+        bf16frag af[4], bfr[4];
+        TrFrag tf[4];
+        const uint32_t b0 = lds_addr(tb(cur));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tr_issue<ks>(tf[j], b0 + btr_off[j]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = frag_read64(ta(cur), wr * 128 + i * 16, ks, lane);
+        tr_wait(tf);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bfr[j] = tr_frag(tf[j]);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) af[i] = frag_read64(ta(cur), wr * 128 + 64 + i * 16, ks, lane);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i + 4][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i + 4][j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+      };
+      if constexpr (BKN) {
+        ks_step(std::integral_constant<int, 0>{});
+        ks_step(std::integral_constant<int, 1>{});
+      } else {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         bf16frag af[4], bfr[4];
@@ -659,6 +849,8 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
             acc[i + 4][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i + 4][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
       }
+      }
+      if constexpr (BKN) VMCNT(0);
       __syncthreads();
       cur ^= 1;
     }
@@ -687,10 +879,9 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
 static int* vh_gg_sched_ws = nullptr;
 static constexpr int VH_GG_SCHED_MAX_G = 4096;
 
-extern "C" int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
-                                         uint16_t* C, const int64_t* cumsum,
-                                         int G, int64_t N, int64_t K,
-                                         int64_t total_rows, void* stream) {
+static int vh_launch_nk256s(bool b_kn, const uint16_t* A, const uint16_t* B,
+                            uint16_t* C, const int64_t* cumsum, int G,
+                            int64_t N, int64_t K, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   VH_CHECK(K % BK64 == 0, "K %% 64 != 0");
   VH_CHECK(N % 16 == 0, "N %% 16 != 0");
@@ -702,7 +893,8 @@ extern "C" int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
   hipLaunchKernelGGL(k_gg_sched, dim3(1), dim3(64), 0, s, cumsum, G, tiles_n,
                      vh_gg_sched_ws);
   VH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_group_gemm_nk256s, dim3(256), dim3(THREADS8), 131072, s,
+  auto kern = b_kn ? k_group_gemm_nk256s<true> : k_group_gemm_nk256s<false>;
+  hipLaunchKernelGGL(kern, dim3(256), dim3(THREADS8), 131072, s,
                      reinterpret_cast<const bf16_t*>(A),
                      reinterpret_cast<const bf16_t*>(B),
                      reinterpret_cast<bf16_t*>(C), cumsum, G, N, K, tiles_n,
@@ -711,80 +903,53 @@ extern "C" int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
   return 0;
 }
 
+extern "C" int vh_group_gemm_nk256s_bf16(const uint16_t* A, const uint16_t* B,
+                                         uint16_t* C, const int64_t* cumsum,
+                                         int G, int64_t N, int64_t K,
+                                         int64_t total_rows, void* stream) {
+  (void)total_rows;
+  return vh_launch_nk256s(false, A, B, C, cumsum, G, N, K, stream);
+}
+
+extern "C" int vh_group_gemm_nk256s_kn_bf16(const uint16_t* A, const uint16_t* B,
+                                            uint16_t* C, const int64_t* cumsum,
+                                            int G, int64_t N, int64_t K,
+                                            int64_t total_rows, void* stream) {
+  (void)total_rows;
+  return vh_launch_nk256s(true, A, B, C, cumsum, G, N, K, stream);
+}
+
 // ============================================================================
-// Transpose-pad + wg256: the fast wgrad path.
+// wgd256s: the direct wgrad. C[g] (M x N) = A_g^T @ B_g with A [rows, M] and
+// B [rows, N] token-major exactly as autograd hands them over; group g owns
+// rows [cumsum[g-1], cumsum[g]). The reduction index (the token row) is the
+// slow one of BOTH operands, so both are staged as [64 k][256 out] tiles
+// (TStage64) and read with transposing LDS reads: no transposed/padded
+// copies, no temporaries, no helper launches.
 //
-// vh_transpose_pad_bf16 turns [rows, C] (rows grouped by expert via cumsum)
-// into [C, padded_rows] where each group's row-range is zero-padded to a
-// 64-multiple (padded_cumsum, host-computed). One memory-bound LDS-tiled
-// transpose (~2x tensor bytes) buys both wgrad operands a K-contiguous
-// layout, so the wgrad itself runs the 256x256 glds structure (wg256s) instead
-// of the 2x-slower transposed-register staging.
+// Same compute structure as k_group_gemm_nk256s under the same XCD-clustered
+// persistent schedule: every group owns the same tiles_m x tiles_n output
+// tiles (weight-shaped C), so the schedule needs no device prefix — block b
+// (XCD b%8) walks the contiguous tile range [X*L, (X+1)*L) with stride 32,
+// bm-inner, keeping a group's B k-slab hot in its XCD's L2.
+//
+// K range: ceil(count/64) tiles from the group's first row, whatever its
+// alignment. In the last tile the rows at or past the group's end are loaded
+// from the group's own last row (clamped: nothing is read outside the group)
+// and then zeroed in LDS in BOTH operands, so they contribute exactly 0
+// whatever the neighbouring rows hold (0 * NaN would be NaN). Each wave
+// zeroes the rows it staged itself, after its own vmcnt(0) and before the
+// barrier that publishes the tile — no extra barrier, wave-uniform branches.
+// Partial m/n tiles wrap their columns (M, N are 16-multiples, so a 16-out
+// segment never straddles the edge); the surplus is dropped at the store.
 // ============================================================================
 
 namespace {
 
-__global__ void k_transpose_pad(const bf16_t* __restrict__ src,
-                                bf16_t* __restrict__ dst,
-                                const int64_t* __restrict__ cumsum,
-                                const int64_t* __restrict__ padded_cumsum,
-                                int G, int64_t C, int64_t padded_total) {
-  // block: 64 padded-rows x 64 cols tile; 256 threads. [64][72] image:
-  // 144-B rows, 16-B aligned, odd 16-B slot count breaks conflicts.
-  __shared__ __attribute__((aligned(16))) bf16_t t2[64][72];
-
-  int64_t chunk = blockIdx.x;          // which 64-row padded chunk
-  int64_t col0 = (int64_t)blockIdx.y * 64;
-  int64_t p0 = chunk * 64;
-  // find group (binary search — a linear walk was ~G dependent global loads
-  // per block): padded chunks never straddle groups (64-multiples)
-  int lo = 0, hi = G;  // first g with p0 < padded_cumsum[g]
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if (p0 >= padded_cumsum[mid]) lo = mid + 1; else hi = mid;
-  }
-  int g = lo;
-  if (g >= G) return;
-  int64_t pstart = (g > 0) ? padded_cumsum[g - 1] : 0;
-  int64_t sstart = (g > 0) ? cumsum[g - 1] : 0;
-  int64_t kcount = cumsum[g] - sstart;
-  int64_t local0 = p0 - pstart;        // offset within the group
-
-  // read 64 src rows (coalesced: 8 threads x 16 B per row)
-  const int tid = threadIdx.x;
-  for (int r = tid / 8; r < 64; r += 32) {
-    int64_t lr = local0 + r;
-    const int cpos = (tid % 8) * 8;
-    bf16x8 v = {};
-    if (lr < kcount && col0 + cpos < C) {
-      v = *reinterpret_cast<const bf16x8*>(src + (sstart + lr) * C + col0 + cpos);
-    }
-    *reinterpret_cast<bf16x8*>(&t2[r][cpos]) = v;
-  }
-  __syncthreads();
-  // write transposed: dst[col][p0 + r], 16 B per thread along padded rows
-  for (int c = tid / 8; c < 64; c += 32) {
-    int rpos = (tid % 8) * 8;
-    if (col0 + c < C) {
-      bf16x8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v.v[j] = t2[rpos + j][c];
-      *reinterpret_cast<bf16x8*>(dst + (col0 + c) * padded_total + p0 + rpos) = v;
-    }
-  }
-}
-
-// wg256s: C[g][M][N] = A'[:, pg] @ B'[:, pg]^T where A' [M, PR], B' [N, PR]
-// are the transpose-padded operands; group g owns padded-row range pg.
-// Same staging/compute structure as k_group_gemm_nk256s, under the same
-// XCD-clustered persistent schedule: every group owns the same tiles_m x tiles_n output tiles (weight-shaped C), so
-// the schedule needs no device prefix — block b (XCD b%8) walks the
-// contiguous tile range [X*L, (X+1)*L) with stride 32, bm-inner, keeping a
-// group's B' k-slab hot in its XCD's L2.
-__global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wg256s(
+__global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wgd256s(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
-    bf16_t* __restrict__ C, const int64_t* __restrict__ padded_cumsum, int G,
-    int64_t M, int64_t N, int64_t PR, int tiles_m, int tiles_n) {
+    bf16_t* __restrict__ C, const int64_t* __restrict__ cumsum, int G,
+    int64_t M, int64_t N, int tiles_m, int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* sm = reinterpret_cast<bf16_t*>(smem);
   auto ta = [&](int buf) { return sm + buf * 32768; };
@@ -808,8 +973,8 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wg256s(
     const int bm = local % tiles_m;   // bm-inner: consecutive t share bn
     const int bn = local / tiles_m;
 
-    const int64_t p_start = (gid > 0) ? padded_cumsum[gid - 1] : 0;
-    const int64_t klen = padded_cumsum[gid] - p_start;
+    const int64_t row_start = (gid > 0) ? cumsum[gid - 1] : 0;
+    const int cnt = (int)(cumsum[gid] - row_start);
     bf16_t* Cg = C + (int64_t)gid * M * N;
 
     f32x4 acc[8][4];
@@ -818,36 +983,61 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wg256s(
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-    if (klen > 0) {
-      const bf16_t* Ag = A + p_start;
-      const bf16_t* Bg = B + p_start;
-      KStage64 sa, sb;
-      sa.init(Ag, PR, [&](int r) -> int64_t {
-        int64_t gm = (int64_t)bm * BM8 + r;
-        return gm % M;
+    if (cnt > 0) {
+      TStage64 sa, sb;
+      sa.init(A + row_start * M, M, [&](int c) -> int64_t {
+        return ((int64_t)bm * BM8 + c) % M;
       }, tid);
-      sb.init(Bg, PR, [&](int r) -> int64_t {
-        int64_t gn = (int64_t)bn * BN8 + r;
-        return gn % N;
+      sb.init(B + row_start * N, N, [&](int c) -> int64_t {
+        return ((int64_t)bn * BN8 + c) % N;
       }, tid);
+      // clamp to the group's last row: in bounds for every k of every tile
+      auto row_of = [&](int k) { return min(k, cnt - 1); };
 
-      const int nk = (int)(klen / BK64);
-      sa.stage(ta(0), 0);
-      sb.stage(tb(0), 0);
+      const int nk = (cnt + BK64 - 1) / BK64;
+      const int rem = cnt - (nk - 1) * BK64;  // valid k-rows of the last tile
+      // stage k-tile kt; the group's last tile gets its tail rows zeroed
+      auto stage = [&](int buf, int kt) {
+        sa.stage(ta(buf), kt * BK64, row_of);
+        sb.stage(tb(buf), kt * BK64, row_of);
+      };
+      auto zero_tail = [&](int buf) {
+        VMCNT(0);
+        sa.zero_tail(ta(buf), rem, lane);
+        sb.zero_tail(tb(buf), rem, lane);
+      };
+
+      int atr_off[8], btr_off[4];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) atr_off[i] = tr_lane_off(wr * 128 + i * 16, lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) btr_off[j] = tr_lane_off(wc * 64 + j * 16, lane);
+
+      stage(0, 0);
+      if (nk == 1 && rem < BK64) zero_tail(0);
+      VMCNT(0);
       __syncthreads();
       int cur = 0;
       for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) {
-          sa.stage(ta(cur ^ 1), (int64_t)(kt + 1) * BK64);
-          sb.stage(tb(cur ^ 1), (int64_t)(kt + 1) * BK64);
-        }
+        if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
+        const uint32_t a0 = lds_addr(ta(cur)), b0 = lds_addr(tb(cur));
+        auto ks_step = [&](auto ks_c) {
+          constexpr int ks = decltype(ks_c)::value;
+          TrFrag tb4[4], ta4[4], ta4h[4];
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
+          for (int j = 0; j < 4; ++j) tr_issue<ks>(tb4[j], b0 + btr_off[j]);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) tr_issue<ks>(ta4[i], a0 + atr_off[i]);
+          tr_wait(tb4);
+          tr_wait(ta4);
+          // the second 64 rows' fragments land under the first MFMA cluster
+#pragma unroll
+          for (int i = 0; i < 4; ++i) tr_issue<ks>(ta4h[i], a0 + atr_off[4 + i]);
           bf16frag af[4], bfr[4];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) bfr[j] = frag_read64(tb(cur), wc * 64 + j * 16, ks, lane);
+          for (int j = 0; j < 4; ++j) bfr[j] = tr_frag(tb4[j]);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) af[i] = frag_read64(ta(cur), wr * 128 + i * 16, ks, lane);
+          for (int i = 0; i < 4; ++i) af[i] = tr_frag(ta4[i]);
           __builtin_amdgcn_s_setprio(1);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
@@ -855,8 +1045,9 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wg256s(
             for (int j = 0; j < 4; ++j)
               acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
           __builtin_amdgcn_s_setprio(0);
+          tr_wait(ta4h);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) af[i] = frag_read64(ta(cur), wr * 128 + 64 + i * 16, ks, lane);
+          for (int i = 0; i < 4; ++i) af[i] = tr_frag(ta4h[i]);
           __builtin_amdgcn_s_setprio(1);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
@@ -864,12 +1055,14 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wg256s(
             for (int j = 0; j < 4; ++j)
               acc[i + 4][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i + 4][j], 0, 0, 0);
           __builtin_amdgcn_s_setprio(0);
-        }
+        };
+        ks_step(std::integral_constant<int, 0>{});
+        ks_step(std::integral_constant<int, 1>{});
+        if (kt + 2 == nk && rem < BK64) zero_tail(cur ^ 1);
+        VMCNT(0);
         __syncthreads();
         cur ^= 1;
       }
-    } else {
-      // keep barrier parity with peer waves (none needed: no LDS touched)
     }
 
     const int col_in = lane & 15;
@@ -890,37 +1083,21 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wg256s(
 
 }  // namespace
 
-extern "C" int vh_transpose_pad_bf16(const uint16_t* src, uint16_t* dst,
-                                     const int64_t* cumsum,
-                                     const int64_t* padded_cumsum, int G,
-                                     int64_t C, int64_t padded_total,
-                                     void* stream) {
+extern "C" int vh_group_gemm_wgd_bf16(const uint16_t* A, const uint16_t* B,
+                                      uint16_t* C, const int64_t* cumsum, int G,
+                                      int64_t M, int64_t N, int64_t total_rows,
+                                      void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  VH_CHECK(C % 8 == 0, "C %% 8 != 0");
-  VH_CHECK(padded_total % 64 == 0, "padded_total %% 64 != 0");
-  dim3 grid((uint32_t)(padded_total / 64), (uint32_t)((C + 63) / 64));
-  hipLaunchKernelGGL(k_transpose_pad, grid, dim3(256), 0, s,
-                     reinterpret_cast<const bf16_t*>(src),
-                     reinterpret_cast<bf16_t*>(dst), cumsum, padded_cumsum, G,
-                     C, padded_total);
-  VH_HIP(hipGetLastError());
-  return 0;
-}
-
-extern "C" int vh_group_gemm_wg256_bf16(const uint16_t* A, const uint16_t* B,
-                                        uint16_t* C,
-                                        const int64_t* padded_cumsum, int G,
-                                        int64_t M, int64_t N, int64_t PR,
-                                        void* stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  VH_CHECK(PR % 64 == 0, "PR %% 64 != 0");
+  (void)total_rows;
+  VH_CHECK(M % 16 == 0 && N % 16 == 0, "M/N %% 16 != 0");
+  VH_CHECK(G >= 1, "G < 1");
   int tiles_m = (int)((M + BM8 - 1) / BM8);
   int tiles_n = (int)((N + BN8 - 1) / BN8);
-  hipLaunchKernelGGL(k_group_gemm_wg256s, dim3(256), dim3(THREADS8), 131072, s,
+  hipLaunchKernelGGL(k_group_gemm_wgd256s, dim3(256), dim3(THREADS8), 131072, s,
                      reinterpret_cast<const bf16_t*>(A),
                      reinterpret_cast<const bf16_t*>(B),
-                     reinterpret_cast<bf16_t*>(C), padded_cumsum, G, M, N, PR,
-                     tiles_m, tiles_n);
+                     reinterpret_cast<bf16_t*>(C), cumsum, G, M, N, tiles_m,
+                     tiles_n);
   VH_HIP(hipGetLastError());
   return 0;
 }

@@ -84,11 +84,11 @@ class HipFusedMoeFunction(torch.autograd.Function):
         grad_output = grad_output.view(-1, grad_output.shape[-1]).contiguous()
 
         grad_fc2_out = hip_lib.moe_scatter(grad_output, scatter_index)
-        # dgrad through fc2 — transpose the (small, persistent) expert weights
-        # once so dgrad runs the fast trans_b kernel (HBM copy ~50 us vs
-        # ~2x slower K-strided dgrad staging; profiles/r01_groupgemm_microbench)
+        # dgrad through fc2 straight from the stored [G, H, I] weights: the
+        # !trans_b nk256s kernel stages W[g] as it lies and transposes in the
+        # LDS read (no transposed copy; profiles/gg_direct_operands_ab.md)
         d_weighted = hip_lib.group_gemm_nk(
-            grad_fc2_out, hip_lib.weight_transpose(fc2_weight), cumsum_t, trans_b=True)
+            grad_fc2_out, fc2_weight, cumsum_t, trans_b=False)
         # wgrad fc2: [G, H, I]
         d_fc2_w = hip_lib.group_gemm_mn(grad_fc2_out, weighted, cumsum_t, G)
 
@@ -99,9 +99,9 @@ class HipFusedMoeFunction(torch.autograd.Function):
         grad_gate = dw_rows[scatter_index.flatten().to(torch.int64)]
         grad_gate = grad_gate.reshape(gate_weights.shape).to(gate_weights.dtype)
 
-        # dgrad + wgrad through merged fc1 (same weight-transpose trick)
+        # dgrad + wgrad through merged fc1 (stored weights, as above)
         d_scatter = hip_lib.group_gemm_nk(
-            d_fc1, hip_lib.weight_transpose(fc1_1_2_weight), cumsum_t, trans_b=True)
+            d_fc1, fc1_1_2_weight, cumsum_t, trans_b=False)
         d_fc1_w = hip_lib.group_gemm_mn(d_fc1, scatter_output, cumsum_t, G)
 
         grad_hidden = hip_lib.moe_gather(d_scatter, scatter_index)
@@ -130,12 +130,10 @@ class EPMergedFc1HipGroupGemm(torch.autograd.Function):
         permute_tokens, cumsum, fc1_1_2_weight, fc2_weight, fc1, act = ctx.saved_tensors
         G = fc2_weight.shape[0]
         grad_output = grad_output.contiguous()
-        d_act = hip_lib.group_gemm_nk(
-            grad_output, hip_lib.weight_transpose(fc2_weight), cumsum, trans_b=True)
+        d_act = hip_lib.group_gemm_nk(grad_output, fc2_weight, cumsum, trans_b=False)
         d_fc2_w = hip_lib.group_gemm_mn(grad_output, act, cumsum, G)
         d_fc1, _ = hip_lib.silu_mul_weighted_bwd(d_act, fc1, None, ctx.swiglu_limit)
-        d_tokens = hip_lib.group_gemm_nk(
-            d_fc1, hip_lib.weight_transpose(fc1_1_2_weight), cumsum, trans_b=True)
+        d_tokens = hip_lib.group_gemm_nk(d_fc1, fc1_1_2_weight, cumsum, trans_b=False)
         d_fc1_w = hip_lib.group_gemm_mn(d_fc1, permute_tokens, cumsum, G)
         return d_tokens, None, d_fc1_w, d_fc2_w, None
 
@@ -152,11 +150,9 @@ def _ep_mlp_fwd(tokens, cumsum, fc1_1_2_weight, fc2_weight, swiglu_limit=None):
 
 def _ep_mlp_bwd_dgrad(dY, cumsum, saved, swiglu_limit=None):
     _, w1, w2, fc1, _ = saved
-    d_act = hip_lib.group_gemm_nk(dY, hip_lib.weight_transpose(w2), cumsum,
-                                  trans_b=True)
+    d_act = hip_lib.group_gemm_nk(dY, w2, cumsum, trans_b=False)
     d_fc1, _ = hip_lib.silu_mul_weighted_bwd(d_act, fc1, None, swiglu_limit)
-    d_tokens = hip_lib.group_gemm_nk(d_fc1, hip_lib.weight_transpose(w1),
-                                     cumsum, trans_b=True)
+    d_tokens = hip_lib.group_gemm_nk(d_fc1, w1, cumsum, trans_b=False)
     return d_tokens, (dY, d_fc1)
 
 

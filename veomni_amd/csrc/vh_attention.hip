@@ -16,15 +16,28 @@
 //     S^T = mfma_32x32x16(A=K, B=Q): lane owns col q = lane&31, 16 f32
 //       scores (the kv rows split across the lane pair);
 //     online softmax per q-col (running m, l lane scalars; cross-half
-//       reduce = one shfl_xor(32)); defer-max (T13, THR=8) skips the
+//       reduce = one v_permlane32_swap): scores scaled into the exp2
+//       domain, row maximum by a v_max3 tree, P = exp2(s*scale2 - m) with
+//       the raw v_exp_f32; defer-max (T13, THR=8) skips the
 //       O-rescale when the wave's max is stable;
-//     P packed to bf16 quads, partner-quad exchange -> A-fragment;
+//     P packed to bf16 pairs (one v_cvt_pk each), partner-quad exchange by
+//       two v_permlane32_swap whose both outputs are used -> A-fragment;
 //     O += mfma(A=P^T, B=V^T (tr16 reads)).
+//   The subtile body exists twice, with and without the causal / document
+//   compare+select per score; a wave-uniform test per kv tile (does the tile
+//   touch the wave's diagonal; varlen: always) picks one. The LDS read
+//   addresses (8 K bases, 8 V bases) are per-lane values carried across the
+//   loop and flipped between the two buffers once per tile; subtile and
+//   16-row chunk select by immediate offsets. Staging sources are a
+//   wave-uniform tile base plus a 32-bit lane offset.
 //   Epilogue: O / l via lane broadcasts; LSE = m + log(l) saved for bwd.
+//   Measurements: profiles/attn_valu_ab.md.
 //
 // LDS: 2x(K 16 + V 16) = 64 KiB.
 
 #include "vh_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -43,6 +56,13 @@ __device__ __forceinline__ void glds16a(const bf16_t* g, bf16_t* l) {
       (__attribute__((address_space(3))) unsigned int*)l, 16, 0, 0);
 }
 
+// one dword per lane: lane i lands at l + i
+__device__ __forceinline__ void glds4(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) unsigned int*)g,
+      (__attribute__((address_space(3))) unsigned int*)l, 4, 0, 0);
+}
+
 // 256-B rows (K, Q tiles): conflict-free slot map for b128 reads
 __device__ __forceinline__ int kswz(int row, int colb) {
   return colb ^ ((row & 15) << 4);
@@ -57,6 +77,40 @@ __device__ __forceinline__ uint32_t swap32_u(uint32_t v, int half) {
 
 __device__ __forceinline__ float xor32h(float v, int half) {
   return __builtin_bit_cast(float, swap32_u(__builtin_bit_cast(uint32_t, v), half));
+}
+
+// Two f32 -> one packed bf16 pair (RNE) in a single v_cvt_pk_bf16_f32;
+// converting the halves one by one costs two converts, a shift and an or.
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+  typedef __attribute__((ext_vector_type(2))) float f32x2t;
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2t;
+  return __builtin_bit_cast(uint32_t,
+                            __builtin_convertvector(f32x2t{lo, hi}, bf16x2t));
+}
+
+// max of three as one v_max3_f32. fmaxf on raw MFMA outputs makes the
+// compiler put a canonicalising v_max_f32 v,v,v in front of every operand;
+// maximumnum has the hardware's own NaN behaviour and needs none. (Not inline
+// asm: the wait states between an MFMA and a VALU read of its result are the
+// compiler's to insert, and it does not look into asm operands; an asm
+// v_max3_f32 here read stale accumulators.)
+__device__ __forceinline__ float max3f(float a, float b, float c) {
+  return __builtin_fmaximum_numf(__builtin_fmaximum_numf(a, b), c);
+}
+
+// Partner-quad exchange of packed bf16 pairs into an MFMA A/B fragment.
+// In: this lane's pairs for kv (or q) rows +0..3 (a0, a1) and +8..11 (c0, c1)
+// of a 16-row chunk; its lane+32 partner holds rows +4..7 and +12..15. Out:
+// 8 consecutive rows, +0..7 in the lower and +8..15 in the upper half-wave.
+// v_permlane32_swap(vdst, src) swaps lanes 32-63 of vdst with lanes 0-31 of
+// src, so swap(a, c) leaves [own a | partner's c] in vdst and [partner's a |
+// own c] in src: both outputs are used and no half-wave select is needed.
+__device__ __forceinline__ bf16frag quad_exchange(uint32_t a0, uint32_t a1,
+                                                  uint32_t c0, uint32_t c1) {
+  auto r0 = __builtin_amdgcn_permlane32_swap(a0, c0, false, false);
+  auto r1 = __builtin_amdgcn_permlane32_swap(a1, c1, false, false);
+  uint4 u{(uint32_t)r0[0], (uint32_t)r1[0], (uint32_t)r0[1], (uint32_t)r1[1]};
+  return __builtin_bit_cast(bf16frag, u);
 }
 
 // DOC: packed-varlen (block-diagonal causal) masking via per-token document
@@ -119,8 +173,10 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
         Qb + q_global * DH + c * 16 + half * 8);
   }
 
-  // ---- persistent staging addresses
-  const bf16_t* ksrc[2];
+  // ---- persistent staging addresses: 32-bit lane offsets, added to the
+  // tile's wave-uniform base (scalar-base global addressing: no 64-bit
+  // per-lane pointers live across the loop)
+  uint32_t ksrc[2];
   int klds[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -128,7 +184,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     int o = base + lane * 16;
     int row = o >> 8;
     int colb = o & 255;
-    ksrc[i] = Kb + (int64_t)row * DH + (kswz(row, colb) >> 1);
+    ksrc[i] = (uint32_t)(row * DH + (kswz(row, colb) >> 1));
     klds[i] = base >> 1;
   }
   f32x16 oacc[4];
@@ -139,11 +195,38 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
 
   const int t_max = (int)(((int64_t)qb * QB + QB - 1) / KB);  // inclusive
 
+  // ---- per-lane LDS read addresses of the current buffer, carried across
+  // the loop and flipped to the other buffer once per tile; sub / mch select
+  // by immediate offsets. K b128 reads: the kswz slot of d-chunk c depends
+  // on the lane's row (col & 15), not on sub -> 8 bases. V tr16 reads: the
+  // L16 slot depends on (kv & 15), which neither sub (32 rows) nor mch (16
+  // rows) changes -> one base per d block and 4-row half.
+  typedef __attribute__((address_space(3))) const char* lds_cptr;
+  lds_cptr kaddr[8], vaddr[4][2];
+  {
+    lds_cptr kt0 = (lds_cptr)kt(0), vt0 = (lds_cptr)vt(0);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      kaddr[c] = kt0 + col * 256 + kswz(col, (c * 16 + half * 8) * 2);
+    const int m_ = lane & 15;
+    const int colhi_ = (lane >> 4) & 1;
+    const int kvb0 = half * 8 + (m_ >> 2);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const int c_r = d * 8 + colhi_ * 4 + (m_ & 3);
+      const int perm_ = (((c_r >> 1) & 3) << 2) | (c_r >> 3);
+      vaddr[d][0] = vt0 + kvb0 * 256 + ((kvb0 & 15) ^ perm_) * 16 + (c_r & 1) * 8;
+      vaddr[d][1] = vt0 + (kvb0 + 4) * 256 + (((kvb0 + 4) & 15) ^ perm_) * 16 +
+                    (c_r & 1) * 8;
+    }
+  }
+  int flip = 16384;  // byte distance to the other buffer
+
   // prologue: stage tile t0 synchronously
   {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      glds16a(ksrc[i] + (int64_t)t0 * KB * DH, kt(0) + klds[i]);
+      glds16a(Kb + (int64_t)t0 * KB * DH + ksrc[i], kt(0) + klds[i]);
     // glds fill of the L16 V image: window win = wave*2+u covers 4 kv rows
     // (1024 B, lane-linear dest); lane sources pair p = P(slot ^ (kv&15))
 #pragma unroll
@@ -152,7 +235,8 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
       const int kvr = win * 4 + (lane >> 4);
       const int pp0 = (lane & 15) ^ (kvr & 15);
       const int pg = ((pp0 & 3) << 2) | (pp0 >> 2);
-      glds16a(Vb + ((int64_t)t0 * KB + kvr) * DH + pg * 8, vt(0) + win * 512);
+      glds16a(Vb + (int64_t)t0 * KB * DH + (uint32_t)(kvr * DH + pg * 8),
+              vt(0) + win * 512);
     }
   }
   __syncthreads();
@@ -163,14 +247,16 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     if (t < t_max) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
-        glds16a(ksrc[i] + (int64_t)(t + 1) * KB * DH, kt(cur ^ 1) + klds[i]);
+        glds16a(Kb + (int64_t)(t + 1) * KB * DH + ksrc[i],
+                kt(cur ^ 1) + klds[i]);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int win = wave * 2 + u;
         const int kvr = win * 4 + (lane >> 4);
         const int pp0 = (lane & 15) ^ (kvr & 15);
         const int pg = ((pp0 & 3) << 2) | (pp0 >> 2);
-        glds16a(Vb + ((int64_t)(t + 1) * KB + kvr) * DH + pg * 8,
+        glds16a(Vb + (int64_t)(t + 1) * KB * DH +
+                    (uint32_t)(kvr * DH + pg * 8),
                 vt(cur ^ 1) + win * 512);
       }
     }
@@ -181,51 +267,60 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     const bool live =
         ((int64_t)t * KB <= (int64_t)qb * QB + wave * WQ + (WQ - 1)) &&
         (!DOC || (int64_t)(t + 1) * KB > ds_wave);
-    const bf16_t* ktc = kt(cur);
-    const bf16_t* vtc = vt(cur);
 
-#pragma unroll
-    for (int sub = 0; sub < 2 && live; ++sub) {
+    // One 32-kv subtile. MASK is a compile-time tag: the masked body applies
+    // the causal (and, for DOC, the document lower-bound) compare+select per
+    // score, the unmasked body has neither. For kv tiles fully below the
+    // diagonal the causal compare never fires, so both bodies compute the
+    // same values there.
+    auto subtile = [&](auto mask_tag, const int sub)
+                       __attribute__((always_inline)) {
+      constexpr bool MASK = decltype(mask_tag)::value;
       // ---- S^T = K·Q^T over 8 d-chunks
       f32x16 sacc = f32x16{};
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        int krow = sub * 32 + col;
-        int colb = (c * 16 + half * 8) * 2;
-        bf16frag kf = *reinterpret_cast<const bf16frag*>(
-            reinterpret_cast<const char*>(ktc) + krow * 256 + kswz(krow, colb));
+        typedef __attribute__((address_space(3))) const bf16frag* lds_frag;
+        bf16frag kf = *(lds_frag)(kaddr[c] + sub * 8192);
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qreg[c], sacc, 0, 0, 0);
       }
 
-      // ---- scale + causal mask in the exp2 domain (scale2 = scale*log2e
-      // folded into the score multiply; v_exp_f32 IS 2^x, so exp2-domain
-      // bookkeeping drops one multiply per element)
+      // ---- scale (+ mask) in the exp2 domain (scale2 = scale*log2e folded
+      // into the score multiply; v_exp_f32 IS 2^x). The product is rounded
+      // before the max-subtract below, two roundings per score: folding them
+      // into one fma is 16 VALU cheaper per subtile but moves O and LSE in
+      // the last bit, which the flagship model amplifies to percents of its
+      // grad norm within one step (profiles/attn_valu_ab.md), so the
+      // roundings stay what they were.
       float p[16];
-      const int kv_lim = (int)(q_global - (int64_t)t * KB) - sub * 32 - 4 * half;
-      const int lo_lim = DOC ? ds_l - (int)((int64_t)t * KB) - sub * 32 - 4 * half
-                             : -2147483647;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float sc = sacc[r] * scale2;
-        int idx = (r & 3) + 8 * (r >> 2);
-        if (diag && idx > kv_lim) sc = -INFINITY;
-        if (DOC && idx < lo_lim) sc = -INFINITY;
-        p[r] = sc;
+      for (int r = 0; r < 16; ++r) p[r] = sacc[r] * scale2;
+      if (MASK) {
+        const int kv_lim =
+            (int)(q_global - (int64_t)t * KB) - sub * 32 - 4 * half;
+        const int lo_lim =
+            DOC ? ds_l - (int)((int64_t)t * KB) - sub * 32 - 4 * half : 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          int idx = (r & 3) + 8 * (r >> 2);
+          if (idx > kv_lim) p[r] = -INFINITY;
+          if (DOC && idx < lo_lim) p[r] = -INFINITY;
+        }
       }
-      float m8[8], m4[4];
+      float m5[5];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) m8[i] = fmaxf(p[2 * i], p[2 * i + 1]);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) m4[i] = fmaxf(m8[2 * i], m8[2 * i + 1]);
-      float mt = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-      mt = fmaxf(mt, xor32h(mt, half));
+      for (int i = 0; i < 5; ++i)
+        m5[i] = max3f(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+      float mt = max3f(max3f(m5[0], m5[1], m5[2]), max3f(m5[3], m5[4], p[15]),
+                       -INFINITY);
+      mt = max3f(mt, xor32h(mt, half), -INFINITY);
 
       // ---- defer-max (T13): rescale only when some lane's max moved past
       // the threshold (wave-uniform decision via ballot)
       bool need = mt > m_run + DEFER_THR;
       if (__builtin_amdgcn_ballot_w64(need) != 0ull) {
         float m_new = fmaxf(m_run, mt);
-        float alpha = __builtin_exp2f(m_run - m_new);
+        float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
         l_run *= alpha;
 #pragma unroll
@@ -237,19 +332,18 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
         }
       }
 
-      // ---- exponentiate + pack pairs + tree row sum
+      // ---- exponentiate + pack pairs + tree row sum. Raw v_exp_f32: it
+      // returns 0 where the result would be an f32 denormal (< 2^-126);
+      // such a probability is below half an ulp of any row sum >= 1 and of
+      // every bf16 P entry, so the flush cannot reach the output.
       float s8[8];
       uint32_t pk[8];
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        float e0 = __builtin_exp2f(p[r] - m_run);
-        float e1 = __builtin_exp2f(p[r + 1] - m_run);
+        float e0 = __builtin_amdgcn_exp2f(p[r] - m_run);
+        float e1 = __builtin_amdgcn_exp2f(p[r + 1] - m_run);
         s8[r >> 1] = e0 + e1;
-        // native bf16 converts (v_cvt) — the integer-emulated RNE rounding
-        // was ~6 VALU ops per element on the hot path
-        uint16_t b0 = __builtin_bit_cast(uint16_t, (__bf16)e0);
-        uint16_t b1 = __builtin_bit_cast(uint16_t, (__bf16)e1);
-        pk[r >> 1] = (uint32_t)b0 | ((uint32_t)b1 << 16);
+        pk[r >> 1] = pack_bf16x2(e0, e1);
       }
       float s4a = (s8[0] + s8[1]) + (s8[2] + s8[3]);
       float s4b = (s8[4] + s8[5]) + (s8[6] + s8[7]);
@@ -260,49 +354,48 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
       // ---- partner-quad exchange -> P^T A-fragments
       bf16frag pa[2];
 #pragma unroll
-      for (int mch = 0; mch < 2; ++mch) {
-        uint32_t s0 = half ? pk[4 * mch] : pk[4 * mch + 2];
-        uint32_t s1 = half ? pk[4 * mch + 1] : pk[4 * mch + 3];
-        uint32_t o0 = swap32_u(s0, half);
-        uint32_t o1 = swap32_u(s1, half);
-        uint32_t w0 = half ? o0 : pk[4 * mch];
-        uint32_t w1 = half ? o1 : pk[4 * mch + 1];
-        uint32_t w2 = half ? pk[4 * mch + 2] : o0;
-        uint32_t w3 = half ? pk[4 * mch + 3] : o1;
-        uint4 u{w0, w1, w2, w3};
-        pa[mch] = __builtin_bit_cast(bf16frag, u);
-      }
+      for (int mch = 0; mch < 2; ++mch)
+        pa[mch] = quad_exchange(pk[4 * mch], pk[4 * mch + 1], pk[4 * mch + 2],
+                                pk[4 * mch + 3]);
 
       // ---- O += P^T · V (B-frags: two 4-kv tr16 reads of the L16 image)
 #pragma unroll
       for (int mch = 0; mch < 2; ++mch) {
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
-          const int m_ = lane & 15;
-          const int colhi_ = (lane >> 4) & 1;
-          const int kvb0 = sub * 32 + mch * 16 + half * 8 + (m_ >> 2);
-          const int c_r = d * 8 + colhi_ * 4 + (m_ & 3);
-          const int perm_ = (((c_r >> 1) & 3) << 2) | (c_r >> 3);
-          const int a0 =
-              kvb0 * 256 + ((kvb0 & 15) ^ perm_) * 16 + (c_r & 1) * 8;
-          const int a1 = (kvb0 + 4) * 256 +
-                         (((kvb0 + 4) & 15) ^ perm_) * 16 + (c_r & 1) * 8;
-          auto* vb3 = (__attribute__((address_space(3))) char*)vtc;
+          const int off = (sub * 32 + mch * 16) * 256;
           typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4t;
           typedef __attribute__((address_space(3))) bf16x4t as3b4;
           bf16x4t r0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-              (as3b4*)(vb3 + a0));
+              (as3b4*)(vaddr[d][0] + off));
           bf16x4t r1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-              (as3b4*)(vb3 + a1));
+              (as3b4*)(vaddr[d][1] + off));
           bf16frag vf =
               __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
           oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[mch], vf, oacc[d], 0, 0, 0);
         }
       }
+    };
+
+    // wave-uniform body choice: varlen always masks (its lower bound can
+    // cut any tile); plain causal masks only on tiles that touch the diagonal
+    if (live) {
+      if (DOC || diag) {
+        subtile(std::true_type{}, 0);
+        subtile(std::true_type{}, 1);
+      } else {
+        subtile(std::false_type{}, 0);
+        subtile(std::false_type{}, 1);
+      }
     }
 
     __syncthreads();
     cur ^= 1;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) kaddr[c] += flip;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) vaddr[d][0] += flip, vaddr[d][1] += flip;
+    flip = -flip;
   }
 
   // ---- epilogue: O / l; bf16 store; LSE
@@ -333,6 +426,8 @@ extern "C" int vh_attn_fwd_bf16(const uint16_t* Q, const uint16_t* K,
   VH_CHECK(S % QB == 0, "S %% 256 != 0 (pad the sequence)");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
   VH_CHECK(doc_start == nullptr || B == 1, "varlen requires packed B == 1");
+  // a softmax scale is positive; zero or negative is a caller's mistake
+  VH_CHECK(scale > 0, "scale must be > 0 (got %g)", (double)scale);
   dim3 grid((uint32_t)(S / QB), (uint32_t)(B * Hq));
   if (doc_start) {
     hipLaunchKernelGGL(k_attn_fwd<true>, grid, dim3(512), 65536, s,
@@ -363,8 +458,12 @@ extern "C" int vh_attn_fwd_bf16(const uint16_t* Q, const uint16_t* K,
 //   k_attn_bwd_dq    — block owns 128 q rows (wave = 32-q slice), loops kv
 //     tiles up to the diagonal; dQ in registers, written once as bf16 (this
 //     block is the only contributor).
-// Scores are recomputed in both kernels: P = exp2(S*scale2 - lse2[q]),
-// dS = P * (dP - delta[q]) * scale. A single kernel that shared the scores
+// Scores are recomputed in both kernels: P = exp2(fma(S, scale2, -lse2[q]))
+// with the raw v_exp_f32, dS = P * (dP - delta[q]) * scale. In both, the
+// P/dS section between the two MFMA chains exists twice, with and without
+// the per-score mask select (tile-local 32-bit compares), picked per tile by
+// a wave-uniform diagonal test (varlen: always masked); the MFMA chains are
+// shared (profiles/attn_valu_ab.md). A single kernel that shared the scores
 // needed a cross-wave dQ reduction through LDS + global atomics, which
 // measured 2-4 ms of pure overhead per call (DESIGN.md, round-1 and round-2
 // attention results; the retired variants are at commit 49b7734).
@@ -427,7 +526,14 @@ __global__ void k_attn_bwd_pre(const bf16_t* __restrict__ dO,
 //     measured -47% cumulative and is bit-identical (DESIGN.md, round-2
 //     outcomes). Register prefetch and register double-buffering of the
 //     staging were measured and lost; see DESIGN.md.
-// LDS 64 KB: K/V strips 2x16 K + Q/dO tiles 2x16 K -> 2 blocks/CU.
+//   - Per tile the 64 lse2 / delta (varlen: doc_start) values of the q tile
+//     are dropped into LDS by one-dword glds next to the images; a lane
+//     fetches the 16 rows its scores belong to with four b128 broadcast
+//     reads per quantity (earlier: two ds_bpermute per score).
+//   - The quadrant body exists twice, chosen per tile by the wave-uniform
+//     `diag`: with and without the per-score mask select.
+// LDS 64.75 KB: K/V strips 2x16 K + Q/dO tiles 2x16 K + 768 B of per-row
+// scalars -> still 2 blocks/CU (160 KiB).
 template <bool DOC>
 __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
@@ -441,6 +547,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
   bf16_t* vrow = reinterpret_cast<bf16_t*>(smem + 16384);    // [64][128] 16 K
   bf16_t* qtr = reinterpret_cast<bf16_t*>(smem + 32768);     // [64][128] L16 16 K
   bf16_t* dotr = reinterpret_cast<bf16_t*>(smem + 49152);    // [64][128] L16 16 K
+  float* stat = reinterpret_cast<float*>(smem + 65536);      // 3 x [64] dwords
   float* red = reinterpret_cast<float*>(smem);               // epilogue reuse
 
   const int kvb = blockIdx.x;          // 64-row kv strip
@@ -521,24 +628,23 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
         const int qrow = win * 4 + (lane >> 4);
         const int pp0 = (lane & 15) ^ (qrow & 15);
         const int pg = ((pp0 & 3) << 2) | (pp0 >> 2);
-        glds16a(Qb + (q0t + qrow) * DH + pg * 8, qtr + win * 512);
-        glds16a(dOb + (q0t + qrow) * DH + pg * 8, dotr + win * 512);
+        // uniform tile base + 32-bit lane offset (scalar-base addressing)
+        const uint32_t loff = (uint32_t)(qrow * DH + pg * 8);
+        glds16a(Qb + q0t * DH + loff, qtr + win * 512);
+        glds16a(dOb + q0t * DH + loff, dotr + win * 512);
       }
+      // the tile's 64 lse2 / delta (and, varlen, doc_start) values go to LDS
+      // next to the images: one dword per lane, waves 0 / 1 / 2
+      if (wave == 0) glds4(lseb + q0t + (uint32_t)lane, stat);
+      else if (wave == 1) glds4(delb + q0t + (uint32_t)lane, stat + 64);
+      else if (DOC && wave == 2)
+        glds4(doc_start + q0t + (uint32_t)lane, stat + 128);
       __syncthreads();
 
       const bool live = ((q0 + 31) >= (kv0 + kvslice * 32)) &&
                         (!DOC || q0 < de_wave);
       const bool diag = (q0 < kv0 + 64);
       if (live) {
-        // per-lane softmax scalars for the lane's own q row; the per-element
-        // values come from cross-lane shuffles below. Reading
-        // lseb[q0+qrm]/delb[q0+qrm] straight from global per element was a
-        // SCATTERED gather (qrm depends on lane>>5) on the critical path
-        // between the s2 MFMA chain and the pack; these two coalesced loads
-        // issue before the MFMA chain and hide under it.
-        const float lse_own = lseb[q0 + col];
-        const float del_own = delb[q0 + col];
-        const int ds_own = DOC ? doc_start[q0 + col] : 0;
         f32x16 s2 = f32x16{}, dp2 = f32x16{};
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -559,46 +665,76 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
           s2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qc, kf, s2, 0, 0, 0);
           dp2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dc, vf, dp2, 0, 0, 0);
         }
+        // P and dS of the quadrant, packed to bf16 pairs. MASK is a
+        // compile-time tag: the masked body applies the causal (and, for
+        // DOC, the document lower-bound) select per score with tile-local
+        // 32-bit indices, the unmasked body has none. Below the diagonal the
+        // causal compare never fires, so both bodies compute the same values
+        // there. Only this section exists twice; the MFMA chains around it
+        // are shared (whole-quadrant duplicates spilled ~120 dwords/lane).
         uint32_t pk2[8], dg2[8];
+        auto pds_pack = [&](auto mask_tag) __attribute__((always_inline)) {
+          constexpr bool MASK = decltype(mask_tag)::value;
+          // tile-local mask bounds: kv row kvl of the strip is masked for q row
+          // idx + 4*half of the subtile when kvl > (q0 - kv0) + idx + 4*half
+          const int kvl = kvslice * 32 + col;
+          const int c_lim = kvl - (int)(q0 - kv0) - 4 * half;
+          const int kv_abs = (int)kv0 + kvl;
+          // per-score softmax scalars: score r belongs to q row
+          // (r&3) + 8*(r>>2) + 4*half of the subtile, i.e. four runs of four
+          // consecutive rows -> one b128 broadcast read per run and quantity.
+          // The runs are kept apart (sched_barrier) so that at most one run's
+          // scalars are live next to the 128 accumulator registers.
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          float pv[2], gv[2];
+          for (int j = 0; j < 4; ++j) {
+            const int qr4 = qsub * 32 + 8 * j + 4 * half;
+            const float4 l4 = *reinterpret_cast<const float4*>(stat + qr4);
+            const float4 d4 = *reinterpret_cast<const float4*>(stat + 64 + qr4);
+            const float lse_q[4] = {l4.x, l4.y, l4.z, l4.w};
+            const float del_q[4] = {d4.x, d4.y, d4.z, d4.w};
+            int ds_q[4] = {0, 0, 0, 0};
+            if (MASK && DOC) {
+              const int4 s4 = *reinterpret_cast<const int4*>(
+                  reinterpret_cast<const int*>(stat) + 128 + qr4);
+              ds_q[0] = s4.x, ds_q[1] = s4.y, ds_q[2] = s4.z, ds_q[3] = s4.w;
+            }
 #pragma unroll
-          for (int rr = 0; rr < 2; ++rr) {
-            int r2 = r + rr;
-            int qrm = (r2 & 3) + 8 * (r2 >> 2) + 4 * half;
-            float lse_q = __shfl(lse_own, qrm, 32);
-            float del_q = __shfl(del_own, qrm, 32);
-            bool masked = diag && ((int64_t)kv0 + kvslice * 32 + col > q0 + qrm);
-            if (DOC)
-              masked = masked ||
-                       ((int64_t)kv0 + kvslice * 32 + col < __shfl(ds_own, qrm, 32));
-            float pp = masked ? 0.f : __builtin_exp2f(s2[r2] * scale2 - lse_q);
-            pv[rr] = pp;
-            gv[rr] = pp * (dp2[r2] - del_q) * scale;
+            for (int h2 = 0; h2 < 2; ++h2) {
+              float pv[2], gv[2];
+#pragma unroll
+              for (int rr = 0; rr < 2; ++rr) {
+                const int i = 2 * h2 + rr;
+                const int r2 = 4 * j + i;
+                // raw v_exp_f32: flushes results below 2^-126 to 0, which is
+                // below the bf16 rounding of every P and dS entry they feed
+                float pp = __builtin_amdgcn_exp2f(
+                    __builtin_fmaf(s2[r2], scale2, -lse_q[i]));
+                if (MASK) {
+                  const int idx = i + 8 * j;
+                  bool masked = idx < c_lim;
+                  if (DOC) masked = masked || (kv_abs < ds_q[i]);
+                  pp = masked ? 0.f : pp;
+                }
+                pv[rr] = pp;
+                gv[rr] = pp * (dp2[r2] - del_q[i]) * scale;
+              }
+              pk2[2 * j + h2] = pack_bf16x2(pv[0], pv[1]);
+              dg2[2 * j + h2] = pack_bf16x2(gv[0], gv[1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
           }
-          pk2[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)pv[0]) |
-                        ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)pv[1]) << 16);
-          dg2[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)gv[0]) |
-                        ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)gv[1]) << 16);
-        }
+        };
+        // wave-uniform choice (varlen always masks: its lower bound can cut
+        // any tile)
+        if (DOC || diag) pds_pack(std::true_type{});
+        else pds_pack(std::false_type{});
         bf16frag pa2[2], da2[2];
 #pragma unroll
         for (int mch = 0; mch < 2; ++mch) {
-          uint32_t a0 = half ? pk2[4 * mch] : pk2[4 * mch + 2];
-          uint32_t a1 = half ? pk2[4 * mch + 1] : pk2[4 * mch + 3];
-          uint32_t b0 = swap32_u(a0, half);
-          uint32_t b1 = swap32_u(a1, half);
-          uint4 u{half ? b0 : pk2[4 * mch], half ? b1 : pk2[4 * mch + 1],
-                  half ? pk2[4 * mch + 2] : b0, half ? pk2[4 * mch + 3] : b1};
-          pa2[mch] = __builtin_bit_cast(bf16frag, u);
-          uint32_t c0 = half ? dg2[4 * mch] : dg2[4 * mch + 2];
-          uint32_t c1 = half ? dg2[4 * mch + 1] : dg2[4 * mch + 3];
-          uint32_t e0 = swap32_u(c0, half);
-          uint32_t e1 = swap32_u(c1, half);
-          uint4 u2{half ? e0 : dg2[4 * mch], half ? e1 : dg2[4 * mch + 1],
-                   half ? dg2[4 * mch + 2] : e0, half ? dg2[4 * mch + 3] : e1};
-          da2[mch] = __builtin_bit_cast(bf16frag, u2);
+          pa2[mch] = quad_exchange(pk2[4 * mch], pk2[4 * mch + 1],
+                                   pk2[4 * mch + 2], pk2[4 * mch + 3]);
+          da2[mch] = quad_exchange(dg2[4 * mch], dg2[4 * mch + 1],
+                                   dg2[4 * mch + 2], dg2[4 * mch + 3]);
         }
         // B-frags: two 4-q hardware-transpose reads per frag from this wave's
         // half of the 64-row image; lane m of each 16-lane group supplies
@@ -685,7 +821,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
 // transpose reads supply the K^T B-frags of dQ += dS^T·K. The three images
 // are DOUBLE buffered (2 x 24 KiB) and filled one kv tile ahead with a
 // single barrier per tile, so the staging drain is off the barrier path
-// (measurements in DESIGN.md, round-2 outcomes).
+// (measurements in DESIGN.md, round-2 outcomes). Per tile: S/dP chain (16
+// MFMA), the dS section (masked or unmasked, see the section header above),
+// pack + partner-quad exchange, dQ chain (8 MFMA). The K/V/K^T read
+// addresses stay base-plus-tile-offset adds: with one 32-row tile per
+// iteration a carried, flipped address costs the same one add per base.
 template <bool DOC>
 __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
@@ -755,11 +895,14 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
       const int row_ = win_ * 4 + (lane >> 4);                                 \
       const int c16_ = (lane & 15) ^ (row_ & 15);                              \
       const int pg_ = (((c16_ & 3) << 2) | (c16_ >> 2));                       \
-      glds16a(Kb + (kv0_ + row_) * DH + c16_ * 8,                              \
+      /* uniform tile base + 32-bit lane offset (scalar-base addressing) */    \
+      const uint32_t lo_ = (uint32_t)(row_ * DH + c16_ * 8);                   \
+      const uint32_t lp_ = (uint32_t)(row_ * DH + pg_ * 8);                    \
+      glds16a(Kb + kv0_ * DH + lo_,                                            \
               reinterpret_cast<bf16_t*>(kb_) + win_ * 512);                    \
-      glds16a(Vb + (kv0_ + row_) * DH + c16_ * 8,                              \
+      glds16a(Vb + kv0_ * DH + lo_,                                            \
               reinterpret_cast<bf16_t*>(kb_ + 8192) + win_ * 512);             \
-      glds16a(Kb + (kv0_ + row_) * DH + pg_ * 8,                               \
+      glds16a(Kb + kv0_ * DH + lp_,                                            \
               reinterpret_cast<bf16_t*>(kb_ + 16384) + win_ * 512);            \
     }                                                                          \
   }
@@ -791,32 +934,50 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
         s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qrow[c], s1, 0, 0, 0);
         dp1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dorow[c], dp1, 0, 0, 0);
       }
+      // dS of the tile, packed to bf16 pairs. MASK is a compile-time tag:
+      // the masked body applies the causal (and, for DOC, the document
+      // lower-bound) select per score with tile-local 32-bit indices, the
+      // unmasked body has none. Below the diagonal the causal compare never
+      // fires, so both bodies compute the same values there. Only this
+      // section exists twice; the MFMA chains around it are shared (whole-
+      // tile duplicates spilled the resident Q/dO fragments).
       uint32_t dg1[8];
+      auto ds_pack = [&](auto mask_tag) __attribute__((always_inline)) {
+        constexpr bool MASK = decltype(mask_tag)::value;
+        // tile-local mask bounds: kv row idx + 4*half of the tile is masked
+        // when it lies past this lane's q row or before its document
+        const int c_lim = (int)(q_l - kvt0) - 4 * half;
+        const int lo_lim = DOC ? ds_l - (int)kvt0 - 4 * half : 0;
 #pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        float g[2];
+        for (int r = 0; r < 16; r += 2) {
+          float g[2];
 #pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-          int r2 = r + rr;
-          int kvl = (r2 & 3) + 8 * (r2 >> 2) + 4 * half;
-          bool masked = diag && (kvt0 + kvl > q_l);
-          if (DOC) masked = masked || (kvt0 + kvl < ds_l);
-          float pp = masked ? 0.f : __builtin_exp2f(s1[r2] * scale2 - lse_l);
-          g[rr] = pp * (dp1[r2] - del_l) * scale;
+          for (int rr = 0; rr < 2; ++rr) {
+            int r2 = r + rr;
+            // raw v_exp_f32: flushes results below 2^-126 to 0, which is
+            // below the bf16 rounding of every dS entry they feed
+            float pp = __builtin_amdgcn_exp2f(
+                __builtin_fmaf(s1[r2], scale2, -lse_l));
+            if (MASK) {
+              const int idx = (r2 & 3) + 8 * (r2 >> 2);
+              bool masked = idx > c_lim;
+              if (DOC) masked = masked || (idx < lo_lim);
+              pp = masked ? 0.f : pp;
+            }
+            g[rr] = pp * (dp1[r2] - del_l) * scale;
+          }
+          dg1[r >> 1] = pack_bf16x2(g[0], g[1]);
         }
-        dg1[r >> 1] = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)g[0]) |
-                      ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)g[1]) << 16);
-      }
+      };
+      // wave-uniform choice (varlen always masks: its lower bound can cut
+      // any tile)
+      if (DOC || diag) ds_pack(std::true_type{});
+      else ds_pack(std::false_type{});
       bf16frag da1[2];
 #pragma unroll
       for (int mch = 0; mch < 2; ++mch) {
-        uint32_t a0 = half ? dg1[4 * mch] : dg1[4 * mch + 2];
-        uint32_t a1 = half ? dg1[4 * mch + 1] : dg1[4 * mch + 3];
-        uint32_t b0 = swap32_u(a0, half);
-        uint32_t b1 = swap32_u(a1, half);
-        uint4 u{half ? b0 : dg1[4 * mch], half ? b1 : dg1[4 * mch + 1],
-                half ? dg1[4 * mch + 2] : b0, half ? dg1[4 * mch + 3] : b1};
-        da1[mch] = __builtin_bit_cast(bf16frag, u);
+        da1[mch] = quad_exchange(dg1[4 * mch], dg1[4 * mch + 1],
+                                 dg1[4 * mch + 2], dg1[4 * mch + 3]);
       }
       // dQ[q][d] += dS1^T(pack) x K^T-tile
 #pragma unroll
@@ -897,7 +1058,7 @@ extern "C" int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
   dim3 grid_kv((uint32_t)(S / 64), (uint32_t)(B * Hkv));
   dim3 grid_q((uint32_t)(S / 128), (uint32_t)(B * Hq));
   auto launch_dkv = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid_kv, dim3(256), 65536, s,
+    hipLaunchKernelGGL(kern, grid_kv, dim3(256), 65536 + 768, s,
                        reinterpret_cast<const bf16_t*>(Q),
                        reinterpret_cast<const bf16_t*>(K),
                        reinterpret_cast<const bf16_t*>(V),

@@ -281,6 +281,39 @@ int vh_ce_fwd_bf16(const uint16_t* logits, const int64_t* labels,
                    int64_t V, float grad_scale, int64_t ignore_index,
                    void* stream);
 
+/* ---- Fused per-token log-probs and entropy ------------------------------- */
+
+/* Per-row log p(label) and softmax entropy over a bf16 logits chunk
+ * [rows, V] (row-contiguous, V % 8 == 0), fp32 math, one read of each row:
+ *   log_probs[r] = f_y - lse,  entropy[r] = lse - sum_j p_j f_j,
+ * both exactly 0 where labels[r] == ignore_index (such rows are not read).
+ * f = logits scaled by inv_temperature in bf16 (skipped when it is 1.0f):
+ * f = bf16(float(x) * inv_temperature). lse / ent_raw (the row statistics
+ * vh_logprob_bwd_bf16 needs; 0 on ignored rows) may be null. No atomics:
+ * bit-reproducible run to run. Labels outside [0, V) other than
+ * ignore_index are never dereferenced and give log_probs = NaN.
+ * Replaces the fp32 [chunk, V] softmax / logsumexp / gather chain of the
+ * reference's chunk_logprobs forward (ref chunk_logprobs.py:165-189). */
+int vh_logprob_fwd_bf16(const uint16_t* logits, const int64_t* labels,
+                        float* log_probs, float* entropy, float* lse,
+                        float* ent_raw, int64_t rows, int64_t V,
+                        float inv_temperature, int64_t ignore_index,
+                        void* stream);
+
+/* Gradient of the above w.r.t. the (unscaled) logits, one pass:
+ *   p_j = exp(f_j - lse),
+ *   dlogits[r,j] = dlp_r (1[j==y_r] - p_j) - dent_r p_j ((f_j - lse_r) + H_r),
+ * rounded once to bf16 and then scaled by inv_temperature in bf16 (skipped
+ * when it is 1.0f). dlog_probs / dentropy may each be null (term dropped);
+ * ignored rows write zeros. lse / ent_raw: the forward's statistics.
+ * Replaces ref chunk_logprobs.py:225-263. */
+int vh_logprob_bwd_bf16(const uint16_t* logits, const int64_t* labels,
+                        const float* lse, const float* ent_raw,
+                        const float* dlog_probs, const float* dentropy,
+                        uint16_t* dlogits, int64_t rows, int64_t V,
+                        float inv_temperature, int64_t ignore_index,
+                        void* stream);
+
 /* ---- Fused MoE load-balancing (aux) loss --------------------------------- */
 
 /* Switch-transformer aux loss over per-layer router logits [T, E] with

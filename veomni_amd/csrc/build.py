@@ -23,6 +23,7 @@ SOURCES = [
     "vh_norms.hip",
     "vh_attention.hip",
     "vh_ce.hip",
+    "vh_logprob.hip",
     "vh_adamw.hip",
     "vh_lbl.hip",
 ]

@@ -604,6 +604,26 @@ class ForCausalLM(nn.Module):
             logits = self.lm_head(hidden)
             return logits, None
 
+        if kwargs.get("return_log_probs", False):
+            # Second half of the ForCausalLMLoss contract (ref cross_entropy/
+            # __init__.py:130-177): per-token log p(y_t) and entropy instead
+            # of a loss; no loss and no aux loss on this path.
+            lp_kwargs = dict(
+                hidden_states=hidden, weights=self.lm_head.weight, labels=labels,
+                shift_labels=kwargs.get("shift_labels"),
+                temperature=kwargs.get("temperature", 1.0),
+            )
+            if kwargs.get("chunk_size") is not None:
+                lp_kwargs["chunk_size"] = kwargs["chunk_size"]
+            if veomni_causal_lm_loss.use_non_eager_impl:
+                _, _, out = veomni_causal_lm_loss(return_log_probs=True, **lp_kwargs)
+                return out
+            from ..model_outputs import FusedLinearAuxOutput
+            from ..ops.kernels.cross_entropy import eager_chunk_logprobs_function
+
+            log_probs, entropy = eager_chunk_logprobs_function(**lp_kwargs)
+            return FusedLinearAuxOutput(log_probs=log_probs, entropy=entropy)
+
         if veomni_causal_lm_loss.use_non_eager_impl:
             # ForCausalLMLoss-shaped 3-tuple contract (ref cross_entropy/
             # __init__.py:89-221): (loss, logits|None, aux|None).

@@ -72,6 +72,10 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_silu_mul_bf16", c_p, c_p, c_p, c_i64, c_p)
     _sig(lib, "vh_silu_mul_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_i64, c_p)
     _sig(lib, "vh_ce_fwd_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_i64, c_p)
+    _sig(lib, "vh_logprob_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64,
+         c_f32, c_i64, c_p)
+    _sig(lib, "vh_logprob_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64,
+         c_i64, c_f32, c_i64, c_p)
     _sig(lib, "vh_adamw_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_f32,
          c_f32, c_f32, c_f32, c_f32, c_int, c_p, c_p)
     _sig(lib, "vh_attn_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int,
@@ -372,6 +376,69 @@ def ce_fwd(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float,
                                        grad_scale, ignore_index, cur_stream()),
               "vh_ce_fwd")
     return loss_rows, dlogits
+
+
+def inv_temperature(temperature: float) -> float:
+    """fp32(1) / fp32(T): the factor ATen's bf16 true-divide by a Python
+    scalar multiplies with; exactly 1.0 for T == 1.0 (kernel skips the scale)."""
+    one = torch.ones((), dtype=torch.float32)
+    return float(one / torch.tensor(float(temperature), dtype=torch.float32))
+
+
+def _check_logprob_args(logits: torch.Tensor, labels: torch.Tensor) -> None:
+    assert logits.dim() == 2 and logits.dtype == torch.bfloat16, \
+        "logprob kernels take bf16 logits [rows, V]"
+    assert logits.is_contiguous(), "logits must be row-contiguous"
+    assert labels.shape == (logits.shape[0],), (labels.shape, logits.shape)
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+
+
+def logprob_fwd(logits: torch.Tensor, labels: torch.Tensor,
+                temperature: float = 1.0, ignore_index: int = -100,
+                want_stats: bool = True):
+    """Per-row (log_probs, entropy, lse, ent_raw), all fp32 [rows]; lse and
+    ent_raw (the statistics logprob_bwd needs) are None without want_stats."""
+    _check_logprob_args(logits, labels)
+    rows, V = logits.shape
+    dev = logits.device
+    log_probs = torch.empty(rows, dtype=torch.float32, device=dev)
+    entropy = torch.empty(rows, dtype=torch.float32, device=dev)
+    lse = torch.empty(rows, dtype=torch.float32, device=dev) if want_stats else None
+    ent_raw = torch.empty(rows, dtype=torch.float32, device=dev) if want_stats else None
+    with _prof("logprob_fwd", 2.0 * rows * V):
+        check(get_lib().vh_logprob_fwd_bf16(
+            dptr(logits), dptr(labels), dptr(log_probs), dptr(entropy),
+            dptr(lse) if want_stats else None,
+            dptr(ent_raw) if want_stats else None,
+            rows, V, inv_temperature(temperature), ignore_index, cur_stream()),
+            "vh_logprob_fwd")
+    return log_probs, entropy, lse, ent_raw
+
+
+def logprob_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor,
+                ent_raw: torch.Tensor, dlp: torch.Tensor | None,
+                dent: torch.Tensor | None, temperature: float = 1.0,
+                ignore_index: int = -100,
+                dlogits_out: torch.Tensor | None = None) -> torch.Tensor:
+    """dlogits (bf16, [rows, V]) from the per-row upstream gradients; a None
+    upstream drops its term."""
+    _check_logprob_args(logits, labels)
+    rows, V = logits.shape
+    for t in (lse, ent_raw, dlp, dent):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (rows,)
+                             and t.is_contiguous())
+    assert lse is not None and ent_raw is not None
+    dlogits = dlogits_out if dlogits_out is not None else torch.empty_like(logits)
+    assert dlogits.is_contiguous() and dlogits.shape == logits.shape \
+        and dlogits.dtype == logits.dtype
+    with _prof("logprob_bwd", 4.0 * rows * V):
+        check(get_lib().vh_logprob_bwd_bf16(
+            dptr(logits), dptr(labels), dptr(lse), dptr(ent_raw),
+            dptr(dlp) if dlp is not None else None,
+            dptr(dent) if dent is not None else None,
+            dptr(dlogits), rows, V, inv_temperature(temperature), ignore_index,
+            cur_stream()), "vh_logprob_bwd")
+    return dlogits
 
 
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,

@@ -6,10 +6,13 @@ Parity targets:
   - chunked fused-linear semantics (never materializes [T,V]):
     chunk_loss.py:43-144 — grads computed IN forward per chunk, saved,
     scaled by upstream grad in backward;
-  - inner CE = fixed_cross_entropy: fp32 log-softmax, sum-NLL / num_items.
+  - inner CE = fixed_cross_entropy: fp32 log-softmax, sum-NLL / num_items;
+  - return_log_probs=True: per-token log p(y_t) and softmax entropy
+    (chunk_logprobs.py), returned as FusedLinearAuxOutput in the third slot.
 
 Device split: chunk logits/dW/dx GEMMs ride hipBLASLt via torch.matmul
-(plain library GEMMs); the softmax/NLL/grad fusion is vh_ce_fwd (C ABI).
+(plain library GEMMs); the softmax/NLL/grad fusion is vh_ce_fwd, the
+log-prob/entropy row pass and its gradient are vh_logprob_fwd/_bwd (C ABI).
 """
 
 from __future__ import annotations
@@ -18,6 +21,7 @@ import torch
 
 from ...distributed.parallel_state import get_parallel_state
 from ...distributed.sequence_parallel import reduce_sequence_parallel_loss
+from ...model_outputs import FusedLinearAuxOutput
 from .. import hip_lib
 from ..kernel_registry import KERNEL_REGISTRY, HardwareRequirement, KernelSpec
 
@@ -88,15 +92,264 @@ class HipChunkCE(torch.autograd.Function):
         return grad_h.reshape(ctx.hshape), grad_w, None, None
 
 
+# --------------------------------------------------------------------------
+# Per-token log-probs + entropy (the return_log_probs half of the contract)
+# --------------------------------------------------------------------------
+def _hip_logprobs_chunks(flat_h, weight, flat_l, temperature, chunk_size,
+                         ignore_index, want_stats):
+    """Chunked lm_head GEMM (bf16, hipBLASLt) + vh_logprob_fwd per chunk.
+    Returns fp32 [T] (log_probs, entropy, lse|None, ent_raw|None)."""
+    if flat_h.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+        raise TypeError(
+            "the hip log-probs path takes bf16 hidden_states and weights, got "
+            f"{flat_h.dtype} / {weight.dtype}; bind the slot 'eager' for other dtypes")
+    T_flat = flat_h.shape[0]
+    parts = []
+    for s in range(0, T_flat, chunk_size):
+        e = min(s + chunk_size, T_flat)
+        logits = torch.matmul(flat_h[s:e], weight.t())
+        parts.append(hip_lib.logprob_fwd(logits, flat_l[s:e], temperature,
+                                         ignore_index, want_stats=want_stats))
+    if not parts:
+        z = torch.zeros(0, dtype=torch.float32, device=flat_h.device)
+        return z, z.clone(), (z.clone() if want_stats else None), \
+            (z.clone() if want_stats else None)
+    cols = [torch.cat(c) if c[0] is not None else None for c in zip(*parts)]
+    return tuple(cols)
+
+
+def _flat_labels(labels):
+    return labels.reshape(-1).to(torch.int64).contiguous()
+
+
+class HipChunkLogProbs(torch.autograd.Function):
+    """(log_probs, entropy) through the lm_head without building [T, V].
+
+    Forward keeps hidden/weight/labels plus the two fp32 [T] row statistics
+    (lse, unmasked entropy); backward re-issues each chunk's logits GEMM
+    exactly as forward did, so vh_logprob_bwd sees the same bf16 logits."""
+
+    @staticmethod
+    def forward(ctx, hidden_states, weight, labels, temperature, chunk_size,
+                ignore_index):
+        ctx.set_materialize_grads(False)
+        flat_h = hidden_states.reshape(-1, hidden_states.shape[-1])
+        flat_l = _flat_labels(labels)
+        lp, ent, lse, raw = _hip_logprobs_chunks(
+            flat_h, weight, flat_l, temperature, chunk_size, ignore_index,
+            want_stats=True)
+        ctx.save_for_backward(flat_h, weight, flat_l, lse, raw)
+        ctx.temperature = temperature
+        ctx.chunk_size = chunk_size
+        ctx.ignore_index = ignore_index
+        ctx.hshape = hidden_states.shape
+        return lp.view(labels.shape), ent.view(labels.shape)
+
+    @staticmethod
+    def backward(ctx, dlog_probs, dentropy):
+        if dlog_probs is None and dentropy is None:
+            return None, None, None, None, None, None
+        flat_h, weight, flat_l, lse, raw = ctx.saved_tensors
+        need_h, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_h or need_w):
+            return None, None, None, None, None, None
+        dlp = (dlog_probs.reshape(-1).float().contiguous()
+               if dlog_probs is not None else None)
+        dent = (dentropy.reshape(-1).float().contiguous()
+                if dentropy is not None else None)
+        T_flat, V = flat_h.shape[0], weight.shape[0]
+        cs = ctx.chunk_size
+        grad_h = torch.empty_like(flat_h) if need_h else None
+        grad_w32 = (torch.zeros(weight.shape, dtype=torch.float32,
+                                device=weight.device) if need_w else None)
+        dlog_buf = flat_h.new_empty((min(cs, T_flat), V))
+        for s in range(0, T_flat, cs):
+            e = min(s + cs, T_flat)
+            h = flat_h[s:e]
+            logits = torch.matmul(h, weight.t())
+            dlog = hip_lib.logprob_bwd(
+                logits, flat_l[s:e], lse[s:e], raw[s:e],
+                dlp[s:e] if dlp is not None else None,
+                dent[s:e] if dent is not None else None,
+                ctx.temperature, ctx.ignore_index, dlogits_out=dlog_buf[:e - s])
+            if need_h:
+                torch.matmul(dlog, weight, out=grad_h[s:e])
+            if need_w:
+                grad_w32 += torch.matmul(dlog.t(), h).float()
+        grad_w = grad_w32.to(weight.dtype) if need_w else None
+        if need_h:
+            grad_h = grad_h.reshape(ctx.hshape)
+        return grad_h, grad_w, None, None, None, None
+
+
+class EagerChunkLogProbs(torch.autograd.Function):
+    """Torch-only twin of HipChunkLogProbs; restates the reference's
+    chunk_logprobs op for op (ref chunk_logprobs.py:165-189, :214-273), any
+    dtype, any device: the temperature divides the logits in the input dtype
+    before the fp32 upcast, dlogits is cast to the input dtype before it is
+    divided, and dweight accumulates across chunks in the weight's dtype."""
+
+    @staticmethod
+    def _chunk_logits(h, weight, temperature):
+        logits = h @ weight.t()
+        if temperature != 1.0:
+            logits = logits / temperature
+        return logits.float()
+
+    @staticmethod
+    def forward(ctx, hidden_states, weight, labels, temperature, chunk_size,
+                ignore_index):
+        ctx.set_materialize_grads(False)
+        flat_h = hidden_states.reshape(-1, hidden_states.shape[-1])
+        flat_l = _flat_labels(labels)
+        T_flat = flat_h.shape[0]
+        lp = torch.zeros(T_flat, dtype=torch.float32, device=flat_h.device)
+        ent = torch.zeros_like(lp)
+        for s in range(0, T_flat, chunk_size):
+            e = min(s + chunk_size, T_flat)
+            logits = EagerChunkLogProbs._chunk_logits(flat_h[s:e], weight,
+                                                      temperature)
+            lab = flat_l[s:e]
+            valid = lab != ignore_index
+            at_label = logits.log_softmax(dim=-1).gather(
+                -1, lab.clamp(min=0).unsqueeze(-1)).squeeze(-1)
+            probs = logits.softmax(dim=-1)
+            H = torch.logsumexp(logits, dim=-1) - torch.sum(probs * logits, dim=-1)
+            lp[s:e] = torch.where(valid, at_label, torch.zeros_like(at_label))
+            ent[s:e] = torch.where(valid, H, torch.zeros_like(H))
+        ctx.save_for_backward(flat_h, weight, flat_l)
+        ctx.temperature = temperature
+        ctx.chunk_size = chunk_size
+        ctx.ignore_index = ignore_index
+        ctx.hshape = hidden_states.shape
+        return lp.view(labels.shape), ent.view(labels.shape)
+
+    @staticmethod
+    def backward(ctx, dlog_probs, dentropy):
+        if dlog_probs is None and dentropy is None:
+            return None, None, None, None, None, None
+        flat_h, weight, flat_l = ctx.saved_tensors
+        need_h, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dlp = dlog_probs.reshape(-1).float() if dlog_probs is not None else None
+        dent = dentropy.reshape(-1).float() if dentropy is not None else None
+        grad_h = torch.zeros_like(flat_h) if need_h else None
+        grad_w = torch.zeros_like(weight) if need_w else None
+        T_flat = flat_h.shape[0]
+        for s in range(0, T_flat, ctx.chunk_size):
+            e = min(s + ctx.chunk_size, T_flat)
+            h = flat_h[s:e]
+            logits = EagerChunkLogProbs._chunk_logits(h, weight, ctx.temperature)
+            lab = flat_l[s:e]
+            valid = (lab != ctx.ignore_index).float()
+            probs = logits.softmax(dim=-1)
+            dlogits = torch.zeros_like(probs)
+            if dlp is not None:
+                onehot = torch.zeros_like(probs).scatter_(
+                    -1, lab.clamp(min=0).unsqueeze(-1), 1.0)
+                dlogits = dlogits + (dlp[s:e] * valid).unsqueeze(-1) * (onehot - probs)
+            if dent is not None:
+                logp = logits.log_softmax(dim=-1)
+                H = torch.logsumexp(logits, dim=-1) - torch.sum(probs * logits, dim=-1)
+                dlogits = dlogits + probs * (logp + H.unsqueeze(-1)) * (
+                    -(dent[s:e] * valid).unsqueeze(-1))
+            dlogits = dlogits.to(h.dtype)
+            if ctx.temperature != 1.0:
+                dlogits = dlogits / ctx.temperature
+            if need_h:
+                grad_h[s:e] = dlogits @ weight
+            if need_w:
+                grad_w += dlogits.t() @ h
+        if need_h:
+            grad_h = grad_h.view(ctx.hshape)
+        return grad_h, grad_w, None, None, None, None
+
+
+def _align_logprobs(hidden_states, labels, shift_labels):
+    """The reference's three alignment modes (ref chunk_logprobs.py:324-343).
+    Returns (hidden, targets, pad): pad says the outputs get one trailing 0."""
+    if shift_labels is not None:          # caller-aligned: used as is
+        return hidden_states, shift_labels, False
+    if get_parallel_state().sp_enabled:   # the SP collator shifted already
+        return hidden_states, labels, False
+    return (hidden_states[..., :-1, :].contiguous(),
+            labels[..., 1:].contiguous(), True)
+
+
+def _pad_logprobs(log_probs, entropy, pad):
+    if pad:
+        log_probs = torch.nn.functional.pad(log_probs, (0, 1), value=0.0)
+        entropy = torch.nn.functional.pad(entropy, (0, 1), value=0.0)
+    return log_probs, entropy
+
+
+def hip_chunk_logprobs_function(hidden_states, weights, labels,
+                                chunk_size: int = 1024,
+                                ignore_index: int = IGNORE_INDEX,
+                                shift_labels=None, temperature: float = 1.0):
+    """Per-token (log_probs, entropy), fp32, shaped like `labels` (or like
+    `shift_labels` when given); 0 at ignored positions and at the pad slot."""
+    hidden_states, targets, pad = _align_logprobs(hidden_states, labels,
+                                                  shift_labels)
+    temperature, chunk_size = float(temperature), int(chunk_size)
+    ignore_index = int(ignore_index)
+    if torch.is_grad_enabled() and (hidden_states.requires_grad
+                                    or weights.requires_grad):
+        lp, ent = HipChunkLogProbs.apply(hidden_states, weights, targets,
+                                         temperature, chunk_size, ignore_index)
+    else:
+        # nothing to differentiate: no row statistics, nothing saved
+        lp, ent, _, _ = _hip_logprobs_chunks(
+            hidden_states.reshape(-1, hidden_states.shape[-1]), weights,
+            _flat_labels(targets), temperature, chunk_size, ignore_index,
+            want_stats=False)
+        lp, ent = lp.view(targets.shape), ent.view(targets.shape)
+    return _pad_logprobs(lp, ent, pad)
+
+
+def eager_chunk_logprobs_function(hidden_states, weights, labels,
+                                  chunk_size: int = 1024,
+                                  ignore_index: int = IGNORE_INDEX,
+                                  shift_labels=None, temperature: float = 1.0):
+    """Torch-only twin of hip_chunk_logprobs_function (impl "eager", CPU
+    tests, GPU baseline)."""
+    hidden_states, targets, pad = _align_logprobs(hidden_states, labels,
+                                                  shift_labels)
+    lp, ent = EagerChunkLogProbs.apply(hidden_states, weights, targets,
+                                       float(temperature), int(chunk_size),
+                                       int(ignore_index))
+    return _pad_logprobs(lp, ent, pad)
+
+
 def hip_causal_lm_loss(hidden_states=None, weights=None, labels=None,
                        vocab_size=None, num_items_in_batch=None,
                        ignore_index=IGNORE_INDEX, shift_labels=None,
-                       chunk_size: int = 2048, **kwargs):
+                       chunk_size: int | None = None,
+                       return_log_probs: bool = False,
+                       temperature: float = 1.0,
+                       teacher_topk_ids=None, teacher_topk_log_probs=None,
+                       **kwargs):
     """ForCausalLMLoss-shaped entry returning (loss, logits|None, aux|None).
 
     Causal shift applied here unless SP pre-shifted the labels in the
-    collator (ref __init__.py:184-195)."""
+    collator (ref __init__.py:184-195). With return_log_probs=True the loss
+    is skipped and the third slot carries FusedLinearAuxOutput(log_probs,
+    entropy) (ref __init__.py:130-177); chunk_size then defaults to 1024,
+    on the loss path to 2048."""
     assert hidden_states is not None and weights is not None
+    if teacher_topk_ids is not None or teacher_topk_log_probs is not None:
+        raise NotImplementedError(
+            "top-k distillation (teacher_topk_ids / teacher_topk_log_probs) "
+            "is not implemented by the hip cross_entropy_loss provider")
+    if return_log_probs:
+        log_probs, entropy = hip_chunk_logprobs_function(
+            hidden_states, weights, labels,
+            chunk_size=1024 if chunk_size is None else chunk_size,
+            ignore_index=ignore_index, shift_labels=shift_labels,
+            temperature=temperature)
+        return None, None, FusedLinearAuxOutput(log_probs=log_probs,
+                                                entropy=entropy)
+    if chunk_size is None:
+        chunk_size = 2048
     sp_enabled = get_parallel_state().sp_enabled
     orig_labels = labels
     if not sp_enabled:
@@ -114,6 +367,7 @@ KERNEL_REGISTRY.register(
         name="hip", op_name="cross_entropy_loss", variant="causal",
         factory=lambda: hip_causal_lm_loss,
         hardware=HardwareRequirement(device_type="gpu"),
-        description="gfx950 chunked fused-linear CE (vh_ce_fwd + hipBLASLt chunks)",
+        description="gfx950 chunked fused-linear CE (vh_ce_fwd + hipBLASLt chunks); "
+                    "return_log_probs via vh_logprob_fwd/_bwd",
     )
 )

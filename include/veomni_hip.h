@@ -314,6 +314,48 @@ int vh_logprob_bwd_bf16(const uint16_t* logits, const int64_t* labels,
                         float inv_temperature, int64_t ignore_index,
                         void* stream);
 
+/* ---- Fused top-k forward-KL distillation --------------------------------- */
+
+/* Per-row top-k forward KL against a teacher given as K ids (int64
+ * [rows, K]) and K log-probs (fp32 [rows, K]), on the same bf16 logits chunk
+ * and with the lse that vh_logprob_fwd_bf16 wrote. With f as above and
+ * s_k = f[ids[r,k]] - lse[r], t_k = tlp[r,k]:
+ *   student_mass[r] = sum_k exp(s_k),  teacher_mass[r] = sum_k exp(t_k),
+ *   distill[r]      = sum_k exp(t'_k) (t'_k - s'_k),
+ * x' = max(x, clamp) when has_clamp != 0, else x; the masses are taken
+ * before the clamp. 1 <= K <= 1024. Rows with labels[r] == ignore_index write
+ * three zeros and read neither ids nor tlp. Every id is range-checked before
+ * it forms an address: one outside [0, V) gives NaN in distill and
+ * student_mass of its row. No atomics: bit-reproducible run to run.
+ * Replaces the fp32 [chunk, V] log_softmax + gather of the reference's
+ * chunk_topk_distill forward (ref chunk_topk_distill.py:170-193). */
+int vh_topk_kl_fwd_bf16(const uint16_t* logits, const int64_t* labels,
+                        const float* lse, const int64_t* ids, const float* tlp,
+                        float* distill, float* student_mass,
+                        float* teacher_mass, int64_t rows, int64_t V,
+                        int64_t K, float inv_temperature, int has_clamp,
+                        float clamp, int64_t ignore_index, void* stream);
+
+/* vh_logprob_bwd_bf16 plus the distillation term, one pass over the row:
+ *   w_k = exp(t'_k) * (has_clamp ? s_k >= clamp : 1),  M = sum_k w_k,
+ *   dlogits[r,j] = dlp_r (1[j==y_r] - p_j) - dent_r p_j ((f_j - lse_r) + H_r)
+ *                + ddist_r (M p_j - sum_{k: ids[r,k]==j} w_k),
+ * summed in fp32, rounded once to bf16, then scaled by inv_temperature in
+ * bf16. Duplicate ids add up; an id may equal the label; ids outside [0, V)
+ * are skipped. Each of the three upstream gradients may be null; with
+ * ddistill null this is vh_logprob_bwd_bf16 (ids / tlp unused). Ignored rows
+ * write zeros and read neither ids nor tlp. No atomics. V < 2^31,
+ * 1 <= K <= 1024. Replaces the dense scatter_add / softmax chain of ref
+ * chunk_topk_distill.py:252-311. */
+int vh_topk_distill_bwd_bf16(const uint16_t* logits, const int64_t* labels,
+                             const float* lse, const float* ent_raw,
+                             const int64_t* ids, const float* tlp,
+                             const float* dlog_probs, const float* dentropy,
+                             const float* ddistill, uint16_t* dlogits,
+                             int64_t rows, int64_t V, int64_t K,
+                             float inv_temperature, int has_clamp, float clamp,
+                             int64_t ignore_index, void* stream);
+
 /* ---- Fused MoE load-balancing (aux) loss --------------------------------- */
 
 /* Switch-transformer aux loss over per-layer router logits [T, E] with

@@ -17,8 +17,11 @@ class FusedLinearAuxOutput:
     """Per-token tensors of a fused lm_head pass that never builds [T, V].
 
     log_probs / entropy: fp32, shape of the labels, exactly 0 at ignored
-    positions. The three distillation fields belong to the top-k
-    distillation path, which this project does not implement; they stay None.
+    positions. distillation_losses / student_mass / teacher_mass: the top-k
+    forward KL against a teacher and the probability mass either side puts
+    on the teacher's top-k ids, same shape and masking; filled only when
+    teacher_topk_ids and teacher_topk_log_probs are given, else None. The
+    two masses are metrics (requires_grad=False).
     """
 
     log_probs: Optional[torch.Tensor] = None

@@ -615,6 +615,32 @@ class ForCausalLM(nn.Module):
             )
             if kwargs.get("chunk_size") is not None:
                 lp_kwargs["chunk_size"] = kwargs["chunk_size"]
+            t_ids = kwargs.get("teacher_topk_ids")
+            t_lp = kwargs.get("teacher_topk_log_probs")
+            if (t_ids is None) != (t_lp is None):
+                raise ValueError(
+                    "teacher_topk_ids and teacher_topk_log_probs must be provided "
+                    "together for the top-k distillation path.")
+            if t_ids is not None:
+                # Third part of the contract (ref __init__.py:144-167): top-k
+                # forward KL against the teacher, next to log-probs / entropy.
+                from ..model_outputs import FusedLinearAuxOutput
+                from ..ops.kernels.cross_entropy import (
+                    eager_chunk_topk_distill_function,
+                    hip_chunk_topk_distill_function,
+                )
+
+                fn = (hip_chunk_topk_distill_function
+                      if veomni_causal_lm_loss.use_non_eager_impl
+                      else eager_chunk_topk_distill_function)
+                log_probs, entropy, distill, s_mass, t_mass = fn(
+                    teacher_topk_ids=t_ids, teacher_topk_log_probs=t_lp,
+                    log_prob_min_clamp=kwargs.get("log_prob_min_clamp"),
+                    **lp_kwargs)
+                return FusedLinearAuxOutput(
+                    log_probs=log_probs, entropy=entropy,
+                    distillation_losses=distill, student_mass=s_mass,
+                    teacher_mass=t_mass)
             if veomni_causal_lm_loss.use_non_eager_impl:
                 _, _, out = veomni_causal_lm_loss(return_log_probs=True, **lp_kwargs)
                 return out

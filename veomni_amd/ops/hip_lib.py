@@ -76,6 +76,10 @@ def get_lib() -> ctypes.CDLL:
          c_f32, c_i64, c_p)
     _sig(lib, "vh_logprob_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64,
          c_i64, c_f32, c_i64, c_p)
+    _sig(lib, "vh_topk_kl_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_i64, c_i64, c_i64, c_f32, c_int, c_f32, c_i64, c_p)
+    _sig(lib, "vh_topk_distill_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_int, c_f32, c_i64, c_p)
     _sig(lib, "vh_adamw_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_f32,
          c_f32, c_f32, c_f32, c_f32, c_int, c_p, c_p)
     _sig(lib, "vh_attn_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int,
@@ -438,6 +442,81 @@ def logprob_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor,
             dptr(dent) if dent is not None else None,
             dptr(dlogits), rows, V, inv_temperature(temperature), ignore_index,
             cur_stream()), "vh_logprob_bwd")
+    return dlogits
+
+
+TOPK_MAX = 1024   # kMaxTopk in vh_logprob.hip: the backward parks K (id, w) pairs in LDS
+
+
+def _check_topk_args(logits: torch.Tensor, ids: torch.Tensor,
+                     tlp: torch.Tensor) -> int:
+    rows = logits.shape[0]
+    assert ids.dim() == 2 and ids.shape[0] == rows, (ids.shape, logits.shape)
+    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    assert tlp.shape == ids.shape and tlp.dtype == torch.float32 \
+        and tlp.is_contiguous(), (tlp.shape, tlp.dtype)
+    K = ids.shape[1]
+    assert 1 <= K <= TOPK_MAX, f"K = {K} outside [1, {TOPK_MAX}]"
+    return K
+
+
+def topk_kl_fwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor,
+                ids: torch.Tensor, tlp: torch.Tensor, temperature: float = 1.0,
+                log_prob_min_clamp: float | None = None,
+                ignore_index: int = -100):
+    """Per-row (distill, student_mass, teacher_mass), fp32 [rows], from the
+    teacher's top-k ids (int64 [rows, K]) and log-probs (fp32 [rows, K]) and
+    the lse logprob_fwd wrote for the same logits and temperature."""
+    _check_logprob_args(logits, labels)
+    K = _check_topk_args(logits, ids, tlp)
+    rows, V = logits.shape
+    assert lse.dtype == torch.float32 and lse.shape == (rows,) and lse.is_contiguous()
+    dev = logits.device
+    distill = torch.empty(rows, dtype=torch.float32, device=dev)
+    student_mass = torch.empty(rows, dtype=torch.float32, device=dev)
+    teacher_mass = torch.empty(rows, dtype=torch.float32, device=dev)
+    has_clamp = log_prob_min_clamp is not None
+    with _prof("topk_kl_fwd", rows * (14.0 * K + 24.0)):
+        check(get_lib().vh_topk_kl_fwd_bf16(
+            dptr(logits), dptr(labels), dptr(lse), dptr(ids), dptr(tlp),
+            dptr(distill), dptr(student_mass), dptr(teacher_mass), rows, V, K,
+            inv_temperature(temperature), int(has_clamp),
+            float(log_prob_min_clamp) if has_clamp else 0.0, ignore_index,
+            cur_stream()), "vh_topk_kl_fwd")
+    return distill, student_mass, teacher_mass
+
+
+def topk_distill_bwd(logits: torch.Tensor, labels: torch.Tensor,
+                     lse: torch.Tensor, ent_raw: torch.Tensor,
+                     ids: torch.Tensor, tlp: torch.Tensor,
+                     dlp: torch.Tensor | None, dent: torch.Tensor | None,
+                     ddist: torch.Tensor | None, temperature: float = 1.0,
+                     log_prob_min_clamp: float | None = None,
+                     ignore_index: int = -100,
+                     dlogits_out: torch.Tensor | None = None) -> torch.Tensor:
+    """logprob_bwd plus the top-k distillation term, one pass; a None
+    upstream drops its term, and ddist=None is logprob_bwd bit for bit."""
+    _check_logprob_args(logits, labels)
+    K = _check_topk_args(logits, ids, tlp)
+    rows, V = logits.shape
+    for t in (lse, ent_raw, dlp, dent, ddist):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (rows,)
+                             and t.is_contiguous())
+    assert lse is not None and ent_raw is not None
+    dlogits = dlogits_out if dlogits_out is not None else torch.empty_like(logits)
+    assert dlogits.is_contiguous() and dlogits.shape == logits.shape \
+        and dlogits.dtype == logits.dtype
+    has_clamp = log_prob_min_clamp is not None
+    with _prof("topk_distill_bwd", 4.0 * rows * V + 18.0 * rows * K):
+        check(get_lib().vh_topk_distill_bwd_bf16(
+            dptr(logits), dptr(labels), dptr(lse), dptr(ent_raw), dptr(ids),
+            dptr(tlp),
+            dptr(dlp) if dlp is not None else None,
+            dptr(dent) if dent is not None else None,
+            dptr(ddist) if ddist is not None else None,
+            dptr(dlogits), rows, V, K, inv_temperature(temperature),
+            int(has_clamp), float(log_prob_min_clamp) if has_clamp else 0.0,
+            ignore_index, cur_stream()), "vh_topk_distill_bwd")
     return dlogits
 
 

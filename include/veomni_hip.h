@@ -198,6 +198,32 @@ int vh_rmsnorm_bwd_bf16(const uint16_t* dy, const uint16_t* x,
                         const uint16_t* w, const float* rstd, uint16_t* dx,
                         float* dw, int64_t T, int64_t H, void* stream);
 
+/* Per-head (H == 128) RMSNorm over strided rows. Every tensor operand is
+ * addressed as base + b*sb + s*ss + head*sh (element strides, multiples of
+ * 8, D contiguous, 16 B aligned base), so x can be the q or k slice of the
+ * fused [B,S,hq+2*hkv,128] qkv projection and y the head-major [B,h,S,128]
+ * tensor RoPE and attention take. rstd fp32 [B*S*h] is indexed by the
+ * logical row (b*S + s)*h + head, as vh_rmsnorm_fwd_bf16 indexes it on a
+ * contiguous [B,S,h,128] copy; y and rstd are bit-equal to that call. */
+int vh_rmsnorm128_fwd_strided_bf16(const uint16_t* x, const uint16_t* w,
+                                   uint16_t* y, float* rstd, int64_t B,
+                                   int64_t S, int64_t h, int64_t x_sb,
+                                   int64_t x_ss, int64_t x_sh, int64_t y_sb,
+                                   int64_t y_ss, int64_t y_sh, float eps,
+                                   void* stream);
+
+/* Backward of the above: dy, x and dx each with their own strides (dx may be
+ * a slice of a qkv-gradient buffer; nothing outside the slice is written).
+ * dx is bit-equal to vh_rmsnorm_bwd_bf16 on contiguous copies and dw (fp32
+ * [128], caller zeroes) gets the same per-wave partials. */
+int vh_rmsnorm128_bwd_strided_bf16(const uint16_t* dy, const uint16_t* x,
+                                   const uint16_t* w, const float* rstd,
+                                   uint16_t* dx, float* dw, int64_t B,
+                                   int64_t S, int64_t h, int64_t dy_sb,
+                                   int64_t dy_ss, int64_t dy_sh, int64_t x_sb,
+                                   int64_t x_ss, int64_t x_sh, int64_t dx_sb,
+                                   int64_t dx_ss, int64_t dx_sh, void* stream);
+
 /* ---- RoPE --------------------------------------------------------------- */
 
 /* In-place-capable rotate-half RoPE on [B, h, S, D] q and k with cos/sin
@@ -255,6 +281,33 @@ int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
                       uint16_t* dV, int B, int Hq, int Hkv, int64_t S,
                       float scale, const int32_t* doc_start,
                       const int32_t* doc_end, void* stream);
+
+/* The three calls above with O (forward, preprocess) and dO (preprocess,
+ * backward) addressed as base + b*sb + hq*sh + row*sr: element strides,
+ * multiples of 8, 128 <= sr <= 2^20, D contiguous, 16 B aligned base.
+ * Token-major [B,S,Hq,128] is {S*Hq*128, 128, Hq*128}, which o_proj reads
+ * as [B,S,Hq*128] without a copy. Q, K, V, dQ, dK, dV, LSE, delta and lse2
+ * keep their head-major layouts; results are bit-equal to the head-major
+ * calls. The preprocess takes one layout for both O and dO. */
+int vh_attn_fwd_ostrided_bf16(const uint16_t* Q, const uint16_t* K,
+                              const uint16_t* V, uint16_t* O, float* LSE,
+                              int B, int Hq, int Hkv, int64_t S, float scale,
+                              const int32_t* doc_start, int64_t o_sb,
+                              int64_t o_sh, int64_t o_sr, void* stream);
+
+int vh_attn_bwd_pre_ostrided_bf16(const uint16_t* dO, const uint16_t* O,
+                                  const float* LSE, float* delta, float* lse2,
+                                  int B, int Hq, int64_t S, int64_t o_sb,
+                                  int64_t o_sh, int64_t o_sr, void* stream);
+
+int vh_attn_bwd2_ostrided_bf16(const uint16_t* Q, const uint16_t* K,
+                               const uint16_t* V, const uint16_t* dO,
+                               const float* delta, const float* lse2,
+                               uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B,
+                               int Hq, int Hkv, int64_t S, float scale,
+                               const int32_t* doc_start,
+                               const int32_t* doc_end, int64_t do_sb,
+                               int64_t do_sh, int64_t do_sr, void* stream);
 
 /* ---- Fused optimizer ----------------------------------------------------- */
 

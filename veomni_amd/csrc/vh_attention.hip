@@ -113,6 +113,20 @@ __device__ __forceinline__ bf16frag quad_exchange(uint32_t a0, uint32_t a1,
   return __builtin_bit_cast(bf16frag, u);
 }
 
+// Where O (forward) and dO (backward) live: element strides of the batch,
+// head and row indices, D contiguous. Head-major [B,Hq,S,D] is {Hq*S*DH,
+// S*DH, DH}; token-major [B,S,Hq,D] (what o_proj reads as [B,S,Hq*D] without
+// a copy) is {S*Hq*DH, DH, Hq*DH}. Runtime values, not a template parameter:
+// tile bases stay wave-uniform, lane offsets 32-bit, and the kernels keep
+// one instantiation per DOC. Q, K, V, dQ, dK, dV and the per-row statistics
+// are head-major always.
+struct OStrides {
+  int64_t sb, sh, sr;
+};
+__host__ inline OStrides head_major(int Hq, int64_t S) {
+  return OStrides{(int64_t)Hq * S * DH, S * DH, DH};
+}
+
 // DOC: packed-varlen (block-diagonal causal) masking via per-token document
 // start indices (doc_start[t] = cu_seqlens[i] for t in document i; B == 1).
 // Replaces the reference's flash-attn varlen cu_seqlens path
@@ -125,7 +139,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
     float* __restrict__ LSE, const int* __restrict__ doc_start, int B, int Hq,
-    int Hkv, int64_t S, float scale) {
+    int Hkv, int64_t S, float scale, OStrides os) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto kt = [&](int buf) {                                   // 2 x 16 KiB
     return reinterpret_cast<bf16_t*>(smem + buf * 16384);
@@ -149,7 +163,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
   const bf16_t* Qb = Q + (((int64_t)b * Hq + hq) * S) * DH;
   const bf16_t* Kb = K + (((int64_t)b * Hkv + hkv) * S) * DH;
   const bf16_t* Vb = V + (((int64_t)b * Hkv + hkv) * S) * DH;
-  bf16_t* Ob = O + (((int64_t)b * Hq + hq) * S) * DH;
+  bf16_t* Ob = O + b * os.sb + hq * os.sh;
   float* Lb = LSE + ((int64_t)b * Hq + hq) * S;
 
   const int64_t q_global = (int64_t)qb * QB + wave * WQ + col;
@@ -407,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     int64_t qg = (int64_t)qb * QB + wave * WQ + qr;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
-      Ob[qg * DH + d * 32 + col] = f2bf(oacc[d][r] * inv);
+      Ob[qg * os.sr + d * 32 + col] = f2bf(oacc[d][r] * inv);
     }
   }
   if (half == 0) {
@@ -418,10 +432,21 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
 
 }  // namespace
 
-extern "C" int vh_attn_fwd_bf16(const uint16_t* Q, const uint16_t* K,
-                                const uint16_t* V, uint16_t* O, float* LSE,
-                                int B, int Hq, int Hkv, int64_t S, float scale,
-                                const int32_t* doc_start, void* stream) {
+// strides the kernels can address: 16 B aligned rows (dO is read in b128
+// fragments) and a row stride whose in-tile lane offsets fit 32 bits
+static int check_ostrides(const void* base, int64_t sb, int64_t sh, int64_t sr) {
+  VH_CHECK((reinterpret_cast<uintptr_t>(base) & 15) == 0, "O/dO base not 16 B aligned");
+  VH_CHECK(sb >= 0 && sh >= 0 && sr >= DH, "O/dO strides must be >= 0, row >= 128");
+  VH_CHECK(sb % 8 == 0 && sh % 8 == 0 && sr % 8 == 0, "O/dO strides %% 8 != 0");
+  VH_CHECK(sr <= (1 << 20), "O/dO row stride too large (%lld)", (long long)sr);
+  return 0;
+}
+
+static int attn_fwd_launch(const uint16_t* Q, const uint16_t* K,
+                           const uint16_t* V, uint16_t* O, float* LSE, int B,
+                           int Hq, int Hkv, int64_t S, float scale,
+                           const int32_t* doc_start, OStrides os,
+                           void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   VH_CHECK(S % QB == 0, "S %% 256 != 0 (pad the sequence)");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
@@ -435,17 +460,37 @@ extern "C" int vh_attn_fwd_bf16(const uint16_t* Q, const uint16_t* K,
                        reinterpret_cast<const bf16_t*>(K),
                        reinterpret_cast<const bf16_t*>(V),
                        reinterpret_cast<bf16_t*>(O), LSE, doc_start, B, Hq,
-                       Hkv, S, scale);
+                       Hkv, S, scale, os);
   } else {
     hipLaunchKernelGGL(k_attn_fwd<false>, grid, dim3(512), 65536, s,
                        reinterpret_cast<const bf16_t*>(Q),
                        reinterpret_cast<const bf16_t*>(K),
                        reinterpret_cast<const bf16_t*>(V),
                        reinterpret_cast<bf16_t*>(O), LSE, nullptr, B, Hq, Hkv,
-                       S, scale);
+                       S, scale, os);
   }
   VH_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int vh_attn_fwd_bf16(const uint16_t* Q, const uint16_t* K,
+                                const uint16_t* V, uint16_t* O, float* LSE,
+                                int B, int Hq, int Hkv, int64_t S, float scale,
+                                const int32_t* doc_start, void* stream) {
+  return attn_fwd_launch(Q, K, V, O, LSE, B, Hq, Hkv, S, scale, doc_start,
+                         head_major(Hq, S), stream);
+}
+
+/* vh_attn_fwd_bf16 with O addressed as O + b*o_sb + hq*o_sh + row*o_sr
+ * (element strides, D contiguous); LSE stays [B,Hq,S]. */
+extern "C" int vh_attn_fwd_ostrided_bf16(
+    const uint16_t* Q, const uint16_t* K, const uint16_t* V, uint16_t* O,
+    float* LSE, int B, int Hq, int Hkv, int64_t S, float scale,
+    const int32_t* doc_start, int64_t o_sb, int64_t o_sh, int64_t o_sr,
+    void* stream) {
+  if (int rc = check_ostrides(O, o_sb, o_sh, o_sr)) return rc;
+  return attn_fwd_launch(Q, K, V, O, LSE, B, Hq, Hkv, S, scale, doc_start,
+                         OStrides{o_sb, o_sh, o_sr}, stream);
 }
 
 // ============================================================================
@@ -497,6 +542,41 @@ __global__ void k_attn_bwd_pre(const bf16_t* __restrict__ dO,
   }
 }
 
+// k_attn_bwd_pre with 4 rows per wave (16-lane groups) and strided O/dO.
+// The xor butterfly over offsets 8, 4, 2, 1 gives every lane of a group the
+// sum lane 0 gets from the __shfl_down chain above (same tree; a + b == b + a),
+// so delta is bit-equal. r walks the head-major statistics [B,Hq,S].
+__global__ __launch_bounds__(256) void k_attn_bwd_pre4(
+    const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O,
+    const float* __restrict__ LSE, float* __restrict__ delta,
+    float* __restrict__ lse2, int64_t rows, int64_t S, int Hq, OStrides os) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sub = lane >> 4;
+  const int cl = lane & 15;
+  const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t r0 = gw * 4; r0 < rows; r0 += nw * 4) {
+    const int64_t r = r0 + sub;
+    const bool ok = r < rows;
+    float acc = 0.f;
+    if (ok) {
+      const int64_t s = r % S;
+      const int64_t bh = r / S;
+      const int64_t off = (bh / Hq) * os.sb + (bh % Hq) * os.sh + s * os.sr;
+      bf16x8 a = reinterpret_cast<const bf16x8*>(dO + off)[cl];
+      bf16x8 b = reinterpret_cast<const bf16x8*>(O + off)[cl];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc += bf2f(a.v[j]) * bf2f(b.v[j]);
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+    if (ok && cl == 0) {
+      delta[r] = acc;
+      lse2[r] = LSE[r] * 1.4426950408889634f;
+    }
+  }
+}
+
 // dK/dV: GQA-folded on the 64-kv-strip geometry.
 //   - grid (S/64, B*Hkv): a block owns a 64-row kv strip of ONE KV head and
 //     loops the whole GQA head group (rep = Hq/Hkv) — dK/dV are written ONCE
@@ -541,7 +621,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
     const float* __restrict__ delta, const float* __restrict__ lse2,
     bf16_t* __restrict__ dK, bf16_t* __restrict__ dV,
     const int* __restrict__ doc_start, const int* __restrict__ doc_end, int B,
-    int Hq, int Hkv, int64_t S, float scale) {
+    int Hq, int Hkv, int64_t S, float scale, OStrides dos) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* krow = reinterpret_cast<bf16_t*>(smem);            // [64][128] 16 K
   bf16_t* vrow = reinterpret_cast<bf16_t*>(smem + 16384);    // [64][128] 16 K
@@ -613,7 +693,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
     {
       const int hq = hkv * rep + g;
       const bf16_t* Qb = Q + (((int64_t)b * Hq + hq) * S) * DH;
-      const bf16_t* dOb = dO + (((int64_t)b * Hq + hq) * S) * DH;
+      const bf16_t* dOb = dO + b * dos.sb + hq * dos.sh;
       const float* delb = delta + ((int64_t)b * Hq + hq) * S;
       const float* lseb = lse2 + ((int64_t)b * Hq + hq) * S;
       const int64_t q0t = (int64_t)qt * 64;
@@ -631,7 +711,21 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
         // uniform tile base + 32-bit lane offset (scalar-base addressing)
         const uint32_t loff = (uint32_t)(qrow * DH + pg * 8);
         glds16a(Qb + q0t * DH + loff, qtr + win * 512);
-        glds16a(dOb + q0t * DH + loff, dotr + win * 512);
+      }
+      // dO rows are dos.sr elements apart, so its lane offsets are its own.
+      // They are rebuilt per tile behind an opaque move and issued after the
+      // Q loads: sharing the loop with Q, or letting them hoist, costs VGPRs
+      // the accumulator section does not have (scratch 0 -> 8..64 B/lane).
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int win = wave * 4 + u;
+        uint32_t qrow = win * 4 + (lane >> 4);
+        asm volatile("" : "+v"(qrow));
+        const uint32_t pp0 = (lane & 15) ^ (qrow & 15);
+        const uint32_t pg = ((pp0 & 3) << 2) | (pp0 >> 2);
+        glds16a(dOb + q0t * dos.sr + (uint32_t)(qrow * (uint32_t)dos.sr + pg * 8),
+                dotr + win * 512);
       }
       // the tile's 64 lse2 / delta (and, varlen, doc_start) values go to LDS
       // next to the images: one dword per lane, waves 0 / 1 / 2
@@ -832,7 +926,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
     const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
     const float* __restrict__ delta, const float* __restrict__ lse2,
     bf16_t* __restrict__ dQ, const int* __restrict__ doc_start, int B, int Hq,
-    int Hkv, int64_t S, float scale) {
+    int Hkv, int64_t S, float scale, OStrides dos) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // two buffer sets of 24 KiB (the launch carves 48 KiB), each:
   //   +0     krow [32][128] kswz  8 K
@@ -854,7 +948,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
   const bf16_t* Qb = Q + (((int64_t)b * Hq + hq) * S) * DH;
   const bf16_t* Kb = K + (((int64_t)b * Hkv + hkv) * S) * DH;
   const bf16_t* Vb = V + (((int64_t)b * Hkv + hkv) * S) * DH;
-  const bf16_t* dOb = dO + (((int64_t)b * Hq + hq) * S) * DH;
+  const bf16_t* dOb = dO + b * dos.sb + hq * dos.sh;
   const float* delb = delta + ((int64_t)b * Hq + hq) * S;
   const float* lseb = lse2 + ((int64_t)b * Hq + hq) * S;
   bf16_t* dQb = dQ + (((int64_t)b * Hq + hq) * S) * DH;
@@ -867,7 +961,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     qrow[c] = *reinterpret_cast<const bf16frag*>(Qb + q_l * DH + c * 16 + half * 8);
-    dorow[c] = *reinterpret_cast<const bf16frag*>(dOb + q_l * DH + c * 16 + half * 8);
+    dorow[c] = *reinterpret_cast<const bf16frag*>(dOb + q_l * dos.sr + c * 16 + half * 8);
   }
   const float lse_l = lseb[q_l];
   const float del_l = delb[q_l];
@@ -1038,17 +1132,34 @@ extern "C" int vh_attn_bwd_pre_bf16(const uint16_t* dO, const uint16_t* O,
   return 0;
 }
 
-/* Split backward: GQA-folded dkv (dK/dV [B,Hkv,S,D] written once — no
- * per-Q-head intermediates, no host group sum) + per-Q-head dq.
- * doc_start/doc_end (nullable, B == 1) select the packed-varlen
- * block-diagonal causal mask. */
-extern "C" int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
-                                 const uint16_t* V, const uint16_t* dO,
-                                 const float* delta, const float* lse2,
-                                 uint16_t* dQ, uint16_t* dK, uint16_t* dV,
-                                 int B, int Hq, int Hkv, int64_t S, float scale,
-                                 const int32_t* doc_start,
-                                 const int32_t* doc_end, void* stream) {
+/* vh_attn_bwd_pre_bf16 over O and dO addressed as base + b*sb + hq*sh +
+ * row*sr (one layout for both); delta and lse2 stay [B,Hq,S]. */
+extern "C" int vh_attn_bwd_pre_ostrided_bf16(
+    const uint16_t* dO, const uint16_t* O, const float* LSE, float* delta,
+    float* lse2, int B, int Hq, int64_t S, int64_t o_sb, int64_t o_sh,
+    int64_t o_sr, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = check_ostrides(dO, o_sb, o_sh, o_sr)) return rc;
+  if (int rc = check_ostrides(O, o_sb, o_sh, o_sr)) return rc;
+  int64_t rows = (int64_t)B * Hq * S;
+  int blocks = (int)((rows + 15) / 16);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_attn_bwd_pre4, dim3(blocks), dim3(256), 0, s,
+                     reinterpret_cast<const bf16_t*>(dO),
+                     reinterpret_cast<const bf16_t*>(O), LSE, delta, lse2, rows,
+                     S, Hq, OStrides{o_sb, o_sh, o_sr});
+  VH_HIP(hipGetLastError());
+  return 0;
+}
+
+static int attn_bwd2_launch(const uint16_t* Q, const uint16_t* K,
+                            const uint16_t* V, const uint16_t* dO,
+                            const float* delta, const float* lse2,
+                            uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B,
+                            int Hq, int Hkv, int64_t S, float scale,
+                            const int32_t* doc_start, const int32_t* doc_end,
+                            OStrides dos, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   VH_CHECK(S % 128 == 0, "S %% 128 != 0");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
@@ -1065,7 +1176,7 @@ extern "C" int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
                        reinterpret_cast<const bf16_t*>(dO), delta, lse2,
                        reinterpret_cast<bf16_t*>(dK),
                        reinterpret_cast<bf16_t*>(dV), doc_start, doc_end, B,
-                       Hq, Hkv, S, scale);
+                       Hq, Hkv, S, scale, dos);
   };
   auto launch_dq = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid_q, dim3(256), 49152, s,
@@ -1074,7 +1185,7 @@ extern "C" int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
                        reinterpret_cast<const bf16_t*>(V),
                        reinterpret_cast<const bf16_t*>(dO), delta, lse2,
                        reinterpret_cast<bf16_t*>(dQ), doc_start, B, Hq, Hkv,
-                       S, scale);
+                       S, scale, dos);
   };
   if (doc_start) launch_dkv(k_attn_bwd_dkv_g<true>);
   else launch_dkv(k_attn_bwd_dkv_g<false>);
@@ -1083,4 +1194,33 @@ extern "C" int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
   else launch_dq(k_attn_bwd_dq<false>);
   VH_HIP(hipGetLastError());
   return 0;
+}
+
+/* Split backward: GQA-folded dkv (dK/dV [B,Hkv,S,D] written once — no
+ * per-Q-head intermediates, no host group sum) + per-Q-head dq.
+ * doc_start/doc_end (nullable, B == 1) select the packed-varlen
+ * block-diagonal causal mask. */
+extern "C" int vh_attn_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
+                                 const uint16_t* V, const uint16_t* dO,
+                                 const float* delta, const float* lse2,
+                                 uint16_t* dQ, uint16_t* dK, uint16_t* dV,
+                                 int B, int Hq, int Hkv, int64_t S, float scale,
+                                 const int32_t* doc_start,
+                                 const int32_t* doc_end, void* stream) {
+  return attn_bwd2_launch(Q, K, V, dO, delta, lse2, dQ, dK, dV, B, Hq, Hkv, S,
+                          scale, doc_start, doc_end, head_major(Hq, S), stream);
+}
+
+/* vh_attn_bwd2_bf16 with dO addressed as dO + b*do_sb + hq*do_sh + row*do_sr
+ * (element strides, D contiguous). */
+extern "C" int vh_attn_bwd2_ostrided_bf16(
+    const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* dO,
+    const float* delta, const float* lse2, uint16_t* dQ, uint16_t* dK,
+    uint16_t* dV, int B, int Hq, int Hkv, int64_t S, float scale,
+    const int32_t* doc_start, const int32_t* doc_end, int64_t do_sb,
+    int64_t do_sh, int64_t do_sr, void* stream) {
+  if (int rc = check_ostrides(dO, do_sb, do_sh, do_sr)) return rc;
+  return attn_bwd2_launch(Q, K, V, dO, delta, lse2, dQ, dK, dV, B, Hq, Hkv, S,
+                          scale, doc_start, doc_end,
+                          OStrides{do_sb, do_sh, do_sr}, stream);
 }

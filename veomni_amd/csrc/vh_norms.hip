@@ -489,6 +489,201 @@ extern "C" int vh_rmsnorm_bwd_bf16(const uint16_t* dy, const uint16_t* x,
   return 0;
 }
 
+// ------------------------------------------- per-head RMSNorm on strided rows
+// H = 128 rows addressed as base + b*sb + s*ss + head*sh (strides in bf16x8
+// vectors, D contiguous), so the q/k norms read their slice of the fused qkv
+// GEMM output and write the head-major [B,h,S,D] layout RoPE and attention
+// take, and the backward writes dx into its slice of the qkv gradient: no
+// .contiguous() copies, no slice-backward fill + add. The per-element math is
+// the contiguous kernels' (k_rmsnorm_fwd_small / k_rmsnorm_bwd_small128)
+// line for line; rstd and the dw partials stay indexed by the logical row
+// r = (b*S + s)*h + head.
+struct RowStrides {
+  int64_t sb, ss, sh;
+};
+
+// Forward: 16-lane groups, 4 rows per wave. The xor butterfly over offsets
+// 8, 4, 2, 1 is the summation tree lane 0 sees in k_rmsnorm_fwd_small's
+// 64-lane __shfl_down with lanes 16..63 holding zero (x + 0 == x), and every
+// lane of a group ends on the same bits because a + b == b + a. Rows are
+// walked head-major (j = (b*h + head)*S + s) so a wave's y rows are adjacent.
+__global__ __launch_bounds__(256) void k_rmsnorm_fwd_small128_strided(
+    const bf16x8* __restrict__ x, const bf16x8* __restrict__ w,
+    bf16x8* __restrict__ y, float* __restrict__ rstd, int64_t T, int64_t S,
+    int64_t h, RowStrides xs, RowStrides ys, float eps, float invH) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sub = lane >> 4;
+  const int cl = lane & 15;
+  const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const bf16x8 wv = w[cl];
+  for (int64_t j0 = gw * 4; j0 < T; j0 += nw * 4) {
+    const int64_t j = j0 + sub;
+    const bool ok = j < T;
+    int64_t b = 0, head = 0, s = 0;
+    bf16x8 v = {};
+    float ss = 0.f;
+    if (ok) {
+      s = j % S;
+      const int64_t bh = j / S;
+      head = bh % h;
+      b = bh / h;
+      v = x[b * xs.sb + s * xs.ss + head * xs.sh + cl];
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        float f = bf2f(v.v[jj]);
+        ss += f * f;
+      }
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) ss += __shfl_xor(ss, off, kWave);
+    float rs = rsqrtf(ss * invH + eps);
+    if (ok) {
+      if (cl == 0 && rstd != nullptr) rstd[(b * S + s) * h + head] = rs;
+      bf16x8 o;
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        float nh = bf2f(f2bf(bf2f(v.v[jj]) * rs));
+        o.v[jj] = f2bf(bf2f(wv.v[jj]) * nh);
+      }
+      y[b * ys.sb + s * ys.ss + head * ys.sh + cl] = o;
+    }
+  }
+}
+
+// Backward: k_rmsnorm_bwd_small128 with the three row addresses strided. The
+// row-to-wave assignment (and so every dw partial) is the contiguous kernel's.
+__global__ __launch_bounds__(256, 4) void k_rmsnorm_bwd_small128_strided(
+    const bf16x8* __restrict__ dy, const bf16x8* __restrict__ x,
+    const bf16x8* __restrict__ w, const float* __restrict__ rstd,
+    bf16x8* __restrict__ dx, float* __restrict__ dw_scratch, int64_t T,
+    int64_t S, int64_t h, RowStrides dys, RowStrides xs, RowStrides dxs,
+    float invH) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int sub = lane >> 4;   // row within the wave's quad
+  const int cl = lane & 15;    // bf16x8 column
+  const int waves_per_block = blockDim.x / kWave;
+  const int64_t gw = (int64_t)blockIdx.x * waves_per_block + wave;
+  const int64_t nw = (int64_t)gridDim.x * waves_per_block;
+
+  const bf16x8 wv = w[cl];
+  float dw_acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dw_acc[j] = 0.f;
+
+  for (int64_t r0 = gw * 4; r0 < T; r0 += nw * 4) {
+    int64_t r = r0 + sub;
+    bool ok = r < T;
+    bf16x8 d = {}, xv = {};
+    float rs = 0.f;
+    int64_t dxo = 0;
+    if (ok) {
+      const int64_t head = r % h;
+      const int64_t t = r / h;
+      const int64_t s = t % S;
+      const int64_t b = t / S;
+      d = dy[b * dys.sb + s * dys.ss + head * dys.sh + cl];
+      xv = x[b * xs.sb + s * xs.ss + head * xs.sh + cl];
+      dxo = b * dxs.sb + s * dxs.ss + head * dxs.sh + cl;
+      rs = rstd[r];
+    }
+    float dot = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      dot += bf2f(d.v[j]) * bf2f(wv.v[j]) * bf2f(xv.v[j]);
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) dot += __shfl_xor(dot, off, kWave);
+    float kf = dot * rs * rs * invH;
+    if (ok) {
+      bf16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float xf = bf2f(xv.v[j]);
+        float g = bf2f(d.v[j]) * bf2f(wv.v[j]);
+        o.v[j] = f2bf(rs * (g - xf * kf));
+        float xhat = bf2f(f2bf(xf * rs));
+        dw_acc[j] += bf2f(d.v[j]) * xhat;
+      }
+      dx[dxo] = o;
+    }
+  }
+  // combine the 4 row-subgroups (same columns) before storing
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    dw_acc[j] += __shfl_xor(dw_acc[j], 16, kWave);
+    dw_acc[j] += __shfl_xor(dw_acc[j], 32, kWave);
+  }
+  if (sub == 0) {
+    float* out = dw_scratch + gw * 128;
+    float4* o4 = reinterpret_cast<float4*>(out + cl * 8);
+    o4[0] = float4{dw_acc[0], dw_acc[1], dw_acc[2], dw_acc[3]};
+    o4[1] = float4{dw_acc[4], dw_acc[5], dw_acc[6], dw_acc[7]};
+  }
+}
+
+// element strides -> bf16x8-vector strides; every row must start 16 B aligned
+static bool vh_row_strides(const void* base, int64_t sb, int64_t ss, int64_t sh,
+                           RowStrides* out) {
+  if ((reinterpret_cast<uintptr_t>(base) & 15) || sb % 8 || ss % 8 || sh % 8)
+    return false;
+  *out = RowStrides{sb / 8, ss / 8, sh / 8};
+  return true;
+}
+
+extern "C" int vh_rmsnorm128_fwd_strided_bf16(
+    const uint16_t* x, const uint16_t* w, uint16_t* y, float* rstd, int64_t B,
+    int64_t S, int64_t h, int64_t x_sb, int64_t x_ss, int64_t x_sh,
+    int64_t y_sb, int64_t y_ss, int64_t y_sh, float eps, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RowStrides xs, ys;
+  VH_CHECK(vh_row_strides(x, x_sb, x_ss, x_sh, &xs), "x rows not 16 B aligned");
+  VH_CHECK(vh_row_strides(y, y_sb, y_ss, y_sh, &ys), "y rows not 16 B aligned");
+  int64_t T = B * S * h;
+  int blocks = (int)((T + 15) / 16);
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_rmsnorm_fwd_small128_strided, dim3(blocks), dim3(256), 0,
+                     s, reinterpret_cast<const bf16x8*>(x),
+                     reinterpret_cast<const bf16x8*>(w),
+                     reinterpret_cast<bf16x8*>(y), rstd, T, S, h, xs, ys, eps,
+                     1.0f / 128.0f);
+  VH_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int vh_rmsnorm128_bwd_strided_bf16(
+    const uint16_t* dy, const uint16_t* x, const uint16_t* w, const float* rstd,
+    uint16_t* dx, float* dw, int64_t B, int64_t S, int64_t h, int64_t dy_sb,
+    int64_t dy_ss, int64_t dy_sh, int64_t x_sb, int64_t x_ss, int64_t x_sh,
+    int64_t dx_sb, int64_t dx_ss, int64_t dx_sh, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  RowStrides dys, xs, dxs;
+  VH_CHECK(vh_row_strides(dy, dy_sb, dy_ss, dy_sh, &dys), "dy rows not 16 B aligned");
+  VH_CHECK(vh_row_strides(x, x_sb, x_ss, x_sh, &xs), "x rows not 16 B aligned");
+  VH_CHECK(vh_row_strides(dx, dx_sb, dx_ss, dx_sh, &dxs), "dx rows not 16 B aligned");
+  int64_t T = B * S * h;
+  // the H == 128 geometry of vh_rmsnorm_bwd_bf16, so k_dw_reduce is fed the
+  // same partial rows
+  int blocks_s = (int)((T + 15) / 16);
+  if (blocks_s > 1024) blocks_s = 1024;
+  if (blocks_s < 1) blocks_s = 1;
+  int waves_total = blocks_s * 4;
+  float* scratch = nullptr;
+  VH_HIP(hipMallocAsync(&scratch, (size_t)waves_total * 128 * sizeof(float), s));
+  hipLaunchKernelGGL(k_rmsnorm_bwd_small128_strided, dim3(blocks_s), dim3(256),
+                     0, s, reinterpret_cast<const bf16x8*>(dy),
+                     reinterpret_cast<const bf16x8*>(x),
+                     reinterpret_cast<const bf16x8*>(w), rstd,
+                     reinterpret_cast<bf16x8*>(dx), scratch, T, S, h, dys, xs,
+                     dxs, 1.0f / 128.0f);
+  hipLaunchKernelGGL(k_dw_reduce, dim3(1, 16), dim3(128), 0, s, scratch, dw,
+                     128, waves_total, 16);
+  VH_HIP(hipFreeAsync(scratch, s));
+  VH_HIP(hipGetLastError());
+  return 0;
+}
+
 // -------------------------------------------------------------------- RoPE
 // x: [B, h, S, D]; cos/sin: [B, S, D] bf16 (halves duplicated). Each thread
 // processes one 8-elem chunk of the FIRST half plus its partner chunk in the

@@ -206,6 +206,21 @@ class Attention(nn.Module):
         else:
             self.q_norm = self.k_norm = None
 
+    # "fused": q/k norms on the qkv slices in place and token-major attention
+    # output, where that applies (see _fused_layout_applies); "slots": always
+    # the per-op slots. The two are bit-equal; the switch exists for A/B runs.
+    qkv_layout = "fused"
+
+    def _fused_layout_applies(self, hv, ps, attn_kwargs) -> bool:
+        if not hv.is_cuda:
+            return False
+        from ..ops.kernels import qkv_layout
+        return qkv_layout.fused_path_applies(
+            veomni_rms_norm, veomni_apply_rotary_pos_emb, veomni_attention,
+            qk_norm=self.q_norm is not None, dtype=hv.dtype,
+            head_dim=self.head_dim, seq_len=hv.shape[1],
+            ulysses=ps.ulysses_enabled, attn_kwargs=attn_kwargs)
+
     def forward(self, hidden_states, position_embeddings, **kwargs):
         input_shape = hidden_states.shape[:-1]
         ps = get_parallel_state()
@@ -227,6 +242,25 @@ class Attention(nn.Module):
         qkv = nn.functional.linear(hidden_states, wqkv, bqkv)
         hv = qkv.view(*input_shape, -1, self.head_dim)
         nh, nkv = self.num_heads, self.num_key_value_heads
+        fused = self.qkv_layout == "fused" and hv.dim() == 4 \
+            and self._fused_layout_applies(hv, ps, kwargs)
+        if fused:
+            # hip norm + hip RoPE + hip_flash core: both norms read their
+            # qkv slice in place and assemble the qkv gradient themselves
+            # (ops/kernels/qkv_layout.py), and attention hands back O
+            # token-major; same values as the per-op path, fewer copies
+            from ..ops.kernels import qkv_layout
+            q, k = qkv_layout.hip_qk_norm(
+                hv, self.q_norm.weight, self.k_norm.weight, nh, nkv,
+                self.q_norm.variance_epsilon, self.k_norm.variance_epsilon)
+            v = hv[..., nh + nkv:, :]
+            q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
+            cos, sin = position_embeddings
+            q, k = apply_rotary_pos_emb(q, k, cos, sin)
+            out, _ = veomni_attention(self, q, k, v, None, dropout=0.0,
+                                      scaling=self.scaling,
+                                      token_major_out=True, **kwargs)
+            return self.o_proj(out.reshape(*input_shape, -1))
         q = hv[..., :nh, :]
         k = hv[..., nh:nh + nkv, :]
         v = hv[..., nh + nkv:, :]

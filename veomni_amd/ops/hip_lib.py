@@ -67,6 +67,11 @@ def get_lib() -> ctypes.CDLL:
          c_i64, c_i64, c_int, c_f32, c_p)
     _sig(lib, "vh_rmsnorm_fwd_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p)
     _sig(lib, "vh_rmsnorm_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p)
+    _sig(lib, "vh_rmsnorm128_fwd_strided_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64,
+         c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_p)
+    _sig(lib, "vh_rmsnorm128_bwd_strided_bf16", c_p, c_p, c_p, c_p, c_p, c_p,
+         c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+         c_i64, c_i64, c_p)
     _sig(lib, "vh_rope_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64,
          c_i64, c_i64, c_int, c_p)
     _sig(lib, "vh_silu_mul_bf16", c_p, c_p, c_p, c_i64, c_p)
@@ -87,6 +92,13 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_attn_bwd_pre_bf16", c_p, c_p, c_p, c_p, c_p, c_i64, c_p)
     _sig(lib, "vh_attn_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
+    _sig(lib, "vh_attn_fwd_ostrided_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int,
+         c_int, c_i64, c_f32, c_p, c_i64, c_i64, c_i64, c_p)
+    _sig(lib, "vh_attn_bwd_pre_ostrided_bf16", c_p, c_p, c_p, c_p, c_p, c_int,
+         c_int, c_i64, c_i64, c_i64, c_i64, c_p)
+    _sig(lib, "vh_attn_bwd2_ostrided_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_p, c_p, c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_i64, c_i64,
+         c_i64, c_p)
     _sig(lib, "vh_lbl_fwd", c_p, c_int, c_p, c_i64, c_int, c_int, c_p, c_int, c_p)
     _sig(lib, "vh_lbl_finish", c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_bwd", c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_p)
@@ -336,6 +348,51 @@ def rmsnorm_bwd(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     return dx, dw
 
 
+def _bsh_strides(t: torch.Tensor):
+    """(batch, token, head) element strides of a logical [B,S,h,128] bf16
+    tensor whose last dim is contiguous — any view the strided kernels take."""
+    assert t.dim() == 4 and t.shape[-1] == 128 and t.dtype == torch.bfloat16, \
+        (t.shape, t.dtype)
+    assert t.stride(3) == 1 or t.shape[3] == 1, t.stride()
+    return t.stride(0), t.stride(1), t.stride(2)
+
+
+def rmsnorm128_fwd_strided(x: torch.Tensor, w: torch.Tensor, eps: float,
+                           y: torch.Tensor | None = None):
+    """Per-head RMSNorm of a logical [B,S,h,128] view x (e.g. the q slice of
+    the qkv projection), no copy. y is a logical [B,S,h,128] view as well;
+    by default the transpose of a fresh head-major [B,h,S,128] buffer.
+    Returns (y, rstd fp32 [B*S*h] in (b, s, head) row order)."""
+    B, S, h, D = x.shape
+    if y is None:
+        y = torch.empty(B, h, S, D, dtype=x.dtype, device=x.device).transpose(1, 2)
+    assert y.shape == x.shape
+    rstd = torch.empty(B * S * h, dtype=torch.float32, device=x.device)
+    with _prof("rmsnorm_fwd", 2.0 * B * S * h * D * 2 + B * S * h * D * 2):
+        check(get_lib().vh_rmsnorm128_fwd_strided_bf16(
+            dptr(x), dptr(w.contiguous()), dptr(y), dptr(rstd), B, S, h,
+            *_bsh_strides(x), *_bsh_strides(y), eps, cur_stream()),
+            "vh_rmsnorm128_fwd_strided")
+    return y, rstd
+
+
+def rmsnorm128_bwd_strided(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
+                           rstd: torch.Tensor, dx: torch.Tensor):
+    """Backward of rmsnorm128_fwd_strided: dy, x and dx are logical
+    [B,S,h,128] views; dx (e.g. a slice of the qkv gradient) is written in
+    place and nothing around it is touched. Returns dw fp32 [128]."""
+    B, S, h, D = x.shape
+    assert dy.shape == x.shape and dx.shape == x.shape
+    assert rstd.dtype == torch.float32 and rstd.numel() == B * S * h \
+        and rstd.is_contiguous()
+    dw = torch.zeros(D, dtype=torch.float32, device=x.device)
+    check(get_lib().vh_rmsnorm128_bwd_strided_bf16(
+        dptr(dy), dptr(x), dptr(w.contiguous()), dptr(rstd), dptr(dx), dptr(dw),
+        B, S, h, *_bsh_strides(dy), *_bsh_strides(x), *_bsh_strides(dx),
+        cur_stream()), "vh_rmsnorm128_bwd_strided")
+    return dw
+
+
 def rope(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
          negate_sin: bool = False):
     B, hq, S, D = q.shape
@@ -568,6 +625,66 @@ def attn_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                     dptr(doc_start) if doc_start is not None else None,
                                     dptr(doc_end) if doc_end is not None else None,
                                     cur_stream()), "vh_attn_bwd2")
+    return dq, dk, dv
+
+
+def _bhs_strides(t: torch.Tensor):
+    """(batch, head, row) element strides of a logical [B,Hq,S,128] view."""
+    assert t.dim() == 4 and t.shape[-1] == 128 and t.stride(3) == 1 \
+        and t.dtype == torch.bfloat16, (t.shape, t.stride(), t.dtype)
+    return t.stride(0), t.stride(1), t.stride(2)
+
+
+def attn_fwd_token_major(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                         scale: float, doc_start: torch.Tensor | None = None):
+    """attn_fwd writing O token-major: returns (o [B,S,Hq,128] contiguous,
+    lse [B,Hq,S]). q/k/v as for attn_fwd; the values are attn_fwd's, bit for
+    bit."""
+    B, Hq, S, D = q.shape
+    Hkv = k.shape[1]
+    assert D == 128 and S % 256 == 0, (S, D)
+    if doc_start is not None:
+        assert B == 1 and doc_start.dtype == torch.int32 and doc_start.numel() == S
+    o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+    with _prof("attn_fwd", 2.0 * 2 * S * S * Hq * D * 0.5 * B):
+        check(get_lib().vh_attn_fwd_ostrided_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(o), dptr(lse), B, Hq, Hkv, S, scale,
+            dptr(doc_start) if doc_start is not None else None,
+            *_bhs_strides(o.transpose(1, 2)), cur_stream()), "vh_attn_fwd_ostrided")
+    return o, lse
+
+
+def attn_bwd_token_major(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                         o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
+                         scale: float, doc_start: torch.Tensor | None = None,
+                         doc_end: torch.Tensor | None = None):
+    """attn_bwd with o and do token-major [B,S,Hq,128] (read in place, no
+    head-major copies). Returns head-major (dq, dk, dv), attn_bwd's bits."""
+    B, Hq, S, D = q.shape
+    Hkv = k.shape[1]
+    assert o.shape == (B, S, Hq, D) and o.is_contiguous(), (o.shape, o.stride())
+    assert do.shape == o.shape
+    do = do.contiguous()
+    rows = B * Hq * S
+    delta = torch.empty(rows, dtype=torch.float32, device=q.device)
+    lse2 = torch.empty(rows, dtype=torch.float32, device=q.device)
+    assert (doc_start is None) == (doc_end is None)
+    strides = _bhs_strides(o.transpose(1, 2))
+    lib = get_lib()
+    with _prof("attn_bwd", 3.0 * 2 * 2 * S * S * Hq * D * 0.5 * B):
+        check(lib.vh_attn_bwd_pre_ostrided_bf16(
+            dptr(do), dptr(o), dptr(lse.contiguous()), dptr(delta), dptr(lse2),
+            B, Hq, S, *strides, cur_stream()), "vh_attn_bwd_pre_ostrided")
+        dq = torch.empty(B, Hq, S, D, dtype=torch.bfloat16, device=q.device)
+        dk = torch.empty(B, Hkv, S, D, dtype=torch.bfloat16, device=q.device)
+        dv = torch.empty(B, Hkv, S, D, dtype=torch.bfloat16, device=q.device)
+        check(lib.vh_attn_bwd2_ostrided_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(do), dptr(delta), dptr(lse2),
+            dptr(dq), dptr(dk), dptr(dv), B, Hq, Hkv, S, scale,
+            dptr(doc_start) if doc_start is not None else None,
+            dptr(doc_end) if doc_end is not None else None,
+            *strides, cur_stream()), "vh_attn_bwd2_ostrided")
     return dq, dk, dv
 
 

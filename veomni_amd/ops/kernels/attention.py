@@ -102,32 +102,40 @@ class _HipFlashAttention(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, doc_start, doc_end):
+    def forward(ctx, q, k, v, scale, doc_start, doc_end, token_major=False):
         from .. import hip_lib
-        o, lse = hip_lib.attn_fwd(q.contiguous(), k.contiguous(),
-                                  v.contiguous(), scale, doc_start)
+        # token_major: O is written, saved and differentiated as [B,S,h,D]
+        # (vh_attn_*_ostrided); same values, no layout copies around the call
+        fwd = hip_lib.attn_fwd_token_major if token_major else hip_lib.attn_fwd
+        o, lse = fwd(q.contiguous(), k.contiguous(), v.contiguous(), scale,
+                     doc_start)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
         ctx.docs = (doc_start, doc_end)
+        ctx.token_major = token_major
         return o
 
     @staticmethod
     def backward(ctx, do):
         from .. import hip_lib
         q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = hip_lib.attn_bwd(q, k, v, o, lse, do, ctx.scale,
-                                      *ctx.docs)
-        return dq, dk, dv, None, None, None
+        bwd = hip_lib.attn_bwd_token_major if ctx.token_major else hip_lib.attn_bwd
+        dq, dk, dv = bwd(q, k, v, o, lse, do, ctx.scale, *ctx.docs)
+        return dq, dk, dv, None, None, None, None
 
 
-def hip_flash_attention(q, k, v, scale, doc_start=None, doc_end=None):
-    """[B, h, S, D] bf16 causal attention through the in-repo HIP kernels."""
-    return _HipFlashAttention.apply(q, k, v, scale, doc_start, doc_end)
+def hip_flash_attention(q, k, v, scale, doc_start=None, doc_end=None,
+                        token_major=False):
+    """[B, h, S, D] bf16 causal attention through the in-repo HIP kernels;
+    the output is [B, h, S, D], or [B, S, h, D] with token_major."""
+    return _HipFlashAttention.apply(q, k, v, scale, doc_start, doc_end,
+                                    token_major)
 
 
 def hip_attention_forward(module, query, key, value, attention_mask,
                           dropout=0.0, scaling=None, sliding_window=None,
-                          softcap=None, skip_ulysses=False, **kwargs):
+                          softcap=None, skip_ulysses=False,
+                          token_major_out=False, **kwargs):
     """Slot signature parity: flash.py:153-165. Inputs [B, h, S, D]
     (pre-transpose, HF convention); returns ([B, S_local, h, D] reshaped by
     the caller, None)."""
@@ -163,7 +171,8 @@ def hip_attention_forward(module, query, key, value, attention_mask,
     if core == "hip_flash":
         if scaling is None:
             scaling = q.shape[-1] ** -0.5
-        out = hip_flash_attention(q, k, v, scaling, doc_start, doc_end)
+        out = hip_flash_attention(q, k, v, scaling, doc_start, doc_end,
+                                  token_major=token_major_out)
     else:
         n_rep = q.shape[1] // k.shape[1]
         k = _repeat_kv(k, n_rep)
@@ -183,7 +192,12 @@ def hip_attention_forward(module, query, key, value, attention_mask,
             out = F.scaled_dot_product_attention(q, k, v, attn_mask=None,
                                                  dropout_p=dropout,
                                                  scale=scaling, is_causal=True)
-    out = out.transpose(1, 2)  # [B, S, h, D]
+    if token_major_out:
+        # the caller (Attention.forward) asks for this only where the
+        # hip_flash core runs without Ulysses: out is [B, S, h, D] already
+        assert core == "hip_flash" and not ulysses
+    else:
+        out = out.transpose(1, 2)  # [B, S, h, D]
     if ulysses:
         out = restore_ulysses_output(out, group=ps.ulysses_group)
     return out, None

@@ -309,6 +309,48 @@ int vh_attn_bwd2_ostrided_bf16(const uint16_t* Q, const uint16_t* K,
                                const int32_t* doc_end, int64_t do_sb,
                                int64_t do_sh, int64_t do_sr, void* stream);
 
+/* Sliding-window attention and attention sinks (the reference forwards
+ * sliding_window and s_aux to its flash kernels, attention/flash.py:249-288).
+ * The strided calls above with
+ *   lo, hi  (nullable; bwd2 takes both or neither) int32 [S] key-window
+ *           bounds shared by every batch row, so B > 1 is allowed: row q sees
+ *           keys lo[q] .. q, and key j is seen by rows j .. hi[j]-1. For a
+ *           causal window of W keys inside documents [doc_start, doc_end):
+ *           lo[q] = max(doc_start[q], q-W+1), hi[j] = min(doc_end[j], j+W).
+ *           Both must be monotone non-decreasing with lo[q] <= q < hi[q] <= S
+ *           (the kernels skip whole tiles from them); a packed batch still
+ *           means B == 1, which the caller enforces.
+ *   sinks   (nullable) fp32 [Hq]: one more softmax column per row of head h
+ *           with the logit sinks[h] (natural-log domain, not multiplied by
+ *           scale) and a zero value vector. LSE includes it. The preprocess
+ *           then also writes dsinks[h] = -sum_{b,s} exp(sinks[h] - LSE) *
+ *           delta (fp32 [Hq]) through partials (fp32 [B*Hq*S/256] workspace),
+ *           summed in a fixed order without atomics; with sinks == NULL it is
+ *           vh_attn_bwd_pre_ostrided_bf16. bwd2 needs only the sink-inclusive
+ *           lse2.
+ * All three: S % 256 == 0, scale > 0, the stride rules above. */
+int vh_attn_fwd_win_sink_bf16(const uint16_t* Q, const uint16_t* K,
+                              const uint16_t* V, uint16_t* O, float* LSE,
+                              int B, int Hq, int Hkv, int64_t S, float scale,
+                              const int32_t* lo, const float* sinks,
+                              int64_t o_sb, int64_t o_sh, int64_t o_sr,
+                              void* stream);
+
+int vh_attn_bwd_pre_sink_bf16(const uint16_t* dO, const uint16_t* O,
+                              const float* LSE, const float* sinks,
+                              float* delta, float* lse2, float* dsinks,
+                              float* partials, int B, int Hq, int64_t S,
+                              int64_t o_sb, int64_t o_sh, int64_t o_sr,
+                              void* stream);
+
+int vh_attn_bwd2_win_bf16(const uint16_t* Q, const uint16_t* K,
+                          const uint16_t* V, const uint16_t* dO,
+                          const float* delta, const float* lse2, uint16_t* dQ,
+                          uint16_t* dK, uint16_t* dV, int B, int Hq, int Hkv,
+                          int64_t S, float scale, const int32_t* lo,
+                          const int32_t* hi, int64_t do_sb, int64_t do_sh,
+                          int64_t do_sr, void* stream);
+
 /* ---- Fused optimizer ----------------------------------------------------- */
 
 /* One-sweep AdamW over a device pointer table (torch semantics: decoupled

@@ -134,12 +134,26 @@ __host__ inline OStrides head_major(int Hq, int64_t S) {
 // V image: natural [64 kv][128 d] layout, off(kv,d) = kv*256 + L16*16 +
 // (d&7)*2, L16 = (kv&15) ^ (((p&3)<<2)|(p>>2)), p = d>>3 (the same image
 // k_attn_bwd_dkv_g stages Q/dO in).
-template <bool DOC>
+// The bounds need not come from documents: the kernel only assumes that
+// doc_start is monotone non-decreasing and indexes it by row within the
+// sequence, never by batch, so a causal window of W keys is the same array
+// with max(doc_start[q], q-W+1) in it (vh_attn_fwd_win_sink_bf16).
+// SINK: attention sinks (gpt-oss). Row q of head hq has one more softmax
+// column, with the logit sinks[hq] (fp32, natural-log domain, not multiplied
+// by scale) and a zero value vector. The online softmax simply starts from
+// that column, m_run = sinks[hq]*log2e and l_run = 1, instead of from the
+// empty row (-1e30, 0): the defer-max rescale then treats it like any score
+// seen earlier, so a dominant sink cannot overflow (every later exponent is
+// <= DEFER_THR) and a negligible one is scaled away by the first rescale.
+// LSE includes the sink, which is all the backward kernels need: their
+// P = exp2(s*scale2 - lse2) is then the sink-inclusive probability.
+template <bool DOC, bool SINK>
 __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
     float* __restrict__ LSE, const int* __restrict__ doc_start, int B, int Hq,
-    int Hkv, int64_t S, float scale, OStrides os) {
+    int Hkv, int64_t S, float scale, OStrides os,
+    const float* __restrict__ sinks) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto kt = [&](int buf) {                                   // 2 x 16 KiB
     return reinterpret_cast<bf16_t*>(smem + buf * 16384);
@@ -206,6 +220,10 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
   for (int d = 0; d < 4; ++d) oacc[d] = f32x16{};
   float m_run = -1e30f;
   float l_run = 0.f;
+  if (SINK) {
+    m_run = sinks[hq] * 1.4426950408889634f;
+    l_run = 1.f;
+  }
 
   const int t_max = (int)(((int64_t)qb * QB + QB - 1) / KB);  // inclusive
 
@@ -446,28 +464,30 @@ static int attn_fwd_launch(const uint16_t* Q, const uint16_t* K,
                            const uint16_t* V, uint16_t* O, float* LSE, int B,
                            int Hq, int Hkv, int64_t S, float scale,
                            const int32_t* doc_start, OStrides os,
-                           void* stream) {
+                           void* stream, const float* sinks = nullptr,
+                           bool shared_bounds = false) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   VH_CHECK(S % QB == 0, "S %% 256 != 0 (pad the sequence)");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
-  VH_CHECK(doc_start == nullptr || B == 1, "varlen requires packed B == 1");
+  VH_CHECK(doc_start == nullptr || B == 1 || shared_bounds,
+           "varlen requires packed B == 1");
   // a softmax scale is positive; zero or negative is a caller's mistake
   VH_CHECK(scale > 0, "scale must be > 0 (got %g)", (double)scale);
   dim3 grid((uint32_t)(S / QB), (uint32_t)(B * Hq));
-  if (doc_start) {
-    hipLaunchKernelGGL(k_attn_fwd<true>, grid, dim3(512), 65536, s,
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(512), 65536, s,
                        reinterpret_cast<const bf16_t*>(Q),
                        reinterpret_cast<const bf16_t*>(K),
                        reinterpret_cast<const bf16_t*>(V),
                        reinterpret_cast<bf16_t*>(O), LSE, doc_start, B, Hq,
-                       Hkv, S, scale, os);
+                       Hkv, S, scale, os, sinks);
+  };
+  if (sinks) {
+    if (doc_start) launch(k_attn_fwd<true, true>);
+    else launch(k_attn_fwd<false, true>);
   } else {
-    hipLaunchKernelGGL(k_attn_fwd<false>, grid, dim3(512), 65536, s,
-                       reinterpret_cast<const bf16_t*>(Q),
-                       reinterpret_cast<const bf16_t*>(K),
-                       reinterpret_cast<const bf16_t*>(V),
-                       reinterpret_cast<bf16_t*>(O), LSE, nullptr, B, Hq, Hkv,
-                       S, scale, os);
+    if (doc_start) launch(k_attn_fwd<true, false>);
+    else launch(k_attn_fwd<false, false>);
   }
   VH_HIP(hipGetLastError());
   return 0;
@@ -493,11 +513,31 @@ extern "C" int vh_attn_fwd_ostrided_bf16(
                          OStrides{o_sb, o_sh, o_sr}, stream);
 }
 
+/* vh_attn_fwd_ostrided_bf16 with a key window and attention sinks.
+ * lo (nullable): int32 [S], the first visible key of every row, applied to
+ * every batch row (B > 1 allowed); monotone non-decreasing, lo[q] <= q.
+ * sinks (nullable): fp32 [Hq], one more softmax column per row whose value
+ * vector is zero; LSE includes it. */
+extern "C" int vh_attn_fwd_win_sink_bf16(
+    const uint16_t* Q, const uint16_t* K, const uint16_t* V, uint16_t* O,
+    float* LSE, int B, int Hq, int Hkv, int64_t S, float scale,
+    const int32_t* lo, const float* sinks, int64_t o_sb, int64_t o_sh,
+    int64_t o_sr, void* stream) {
+  if (int rc = check_ostrides(O, o_sb, o_sh, o_sr)) return rc;
+  return attn_fwd_launch(Q, K, V, O, LSE, B, Hq, Hkv, S, scale, lo,
+                         OStrides{o_sb, o_sh, o_sr}, stream, sinks,
+                         /*shared_bounds=*/true);
+}
+
 // ============================================================================
 // Flash attention backward (bf16, causal, GQA, D = 128): split into two
 // kernels that keep every accumulator in registers, with no atomics and no
 // cross-block reduction.
 //   k_attn_bwd_pre   — delta = rowsum(dO*O), lse2 = LSE*log2e.
+//   k_attn_bwd_pre4_sink + k_attn_dsinks_finish — the same plus the
+//     attention-sink gradient; with a sink-inclusive LSE the two kernels
+//     below need no change for sinks, and a key window is their doc_start /
+//     doc_end bounds (vh_attn_bwd2_win_bf16).
 //   k_attn_bwd_dkv_g — block owns a 64-row kv strip of one KV head, loops the
 //     GQA head group and the q tiles from the diagonal; dK/dV in registers.
 //   k_attn_bwd_dq    — block owns 128 q rows (wave = 32-q slice), loops kv
@@ -575,6 +615,71 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pre4(
       lse2[r] = LSE[r] * 1.4426950408889634f;
     }
   }
+}
+
+// k_attn_bwd_pre4 plus the gradient of the attention sinks,
+//   dsinks[h] = -sum_{b,s} exp(sinks[h] - LSE[b,h,s]) * delta[b,h,s]
+// (the sink column's probability times -delta; its dP is 0 because its value
+// vector is zero). Grid (S/256, B*Hq): a block owns 256 rows of one (b, h),
+// wave w and 16-lane group g take row it*16 + w*4 + g of them in pass it, so
+// delta is k_attn_bwd_pre4's bit for bit. Every block writes one partial
+// (part[bh*nblk + blk]); the sums inside a block and in k_attn_dsinks_finish
+// run in a fixed order and use no atomics, so dsinks is the same from run to
+// run and for every O/dO layout.
+__global__ __launch_bounds__(256) void k_attn_bwd_pre4_sink(
+    const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O,
+    const float* __restrict__ LSE, const float* __restrict__ sinks,
+    float* __restrict__ delta, float* __restrict__ lse2,
+    float* __restrict__ part, int64_t S, int Hq, OStrides os) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x >> 6;
+  const int sub = lane >> 4;
+  const int cl = lane & 15;
+  const int64_t bh = blockIdx.y;
+  const int hq = (int)(bh % Hq);
+  const int64_t base = (bh / Hq) * os.sb + hq * os.sh;
+  const float sink = sinks[hq];
+  float gacc = 0.f;   // this 16-lane group's share, the same in its lanes
+  for (int it = 0; it < 16; ++it) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + it * 16 + wave * 4 + sub;
+    const int64_t r = bh * S + s;
+    const int64_t off = base + s * os.sr;
+    bf16x8 a = reinterpret_cast<const bf16x8*>(dO + off)[cl];
+    bf16x8 b = reinterpret_cast<const bf16x8*>(O + off)[cl];
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += bf2f(a.v[j]) * bf2f(b.v[j]);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
+    const float lse = LSE[r];
+    if (cl == 0) {
+      delta[r] = acc;
+      lse2[r] = lse * 1.4426950408889634f;
+    }
+    gacc += expf(sink - lse) * acc;
+  }
+  const float g0 = __shfl(gacc, 0, kWave), g1 = __shfl(gacc, 16, kWave);
+  const float g2 = __shfl(gacc, 32, kWave), g3 = __shfl(gacc, 48, kWave);
+  if (lane == 0) red[wave] = (g0 + g1) + (g2 + g3);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    part[bh * gridDim.x + blockIdx.x] = -((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// dsinks[h] = sum over b, then blocks, of part[(b*Hq + h)*nblk + blk], in
+// that order: one thread per head.
+__global__ void k_attn_dsinks_finish(const float* __restrict__ part,
+                                     float* __restrict__ dsinks, int B, int Hq,
+                                     int nblk) {
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= Hq) return;
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float* p = part + ((int64_t)b * Hq + h) * nblk;
+    for (int i = 0; i < nblk; ++i) acc += p[i];
+  }
+  dsinks[h] = acc;
 }
 
 // dK/dV: GQA-folded on the 64-kv-strip geometry.
@@ -1153,19 +1258,53 @@ extern "C" int vh_attn_bwd_pre_ostrided_bf16(
   return 0;
 }
 
+/* vh_attn_bwd_pre_ostrided_bf16 that also returns the attention-sink
+ * gradient. sinks (nullable, fp32 [Hq]): with it, dsinks (fp32 [Hq]) is
+ * written and partials (fp32 [B*Hq*S/256], workspace) is used; LSE must be
+ * the sink-inclusive one of vh_attn_fwd_win_sink_bf16. Without it the call
+ * is vh_attn_bwd_pre_ostrided_bf16. S % 256 == 0. */
+extern "C" int vh_attn_bwd_pre_sink_bf16(
+    const uint16_t* dO, const uint16_t* O, const float* LSE,
+    const float* sinks, float* delta, float* lse2, float* dsinks,
+    float* partials, int B, int Hq, int64_t S, int64_t o_sb, int64_t o_sh,
+    int64_t o_sr, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  VH_CHECK(S > 0 && S % 256 == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(B > 0 && Hq > 0, "B, Hq must be > 0");
+  if (sinks == nullptr)
+    return vh_attn_bwd_pre_ostrided_bf16(dO, O, LSE, delta, lse2, B, Hq, S,
+                                         o_sb, o_sh, o_sr, stream);
+  VH_CHECK(dsinks != nullptr && partials != nullptr,
+           "sinks need the dsinks output and the partials workspace");
+  if (int rc = check_ostrides(dO, o_sb, o_sh, o_sr)) return rc;
+  if (int rc = check_ostrides(O, o_sb, o_sh, o_sr)) return rc;
+  const int nblk = (int)(S / 256);
+  hipLaunchKernelGGL(k_attn_bwd_pre4_sink, dim3(nblk, (uint32_t)(B * Hq)),
+                     dim3(256), 0, s, reinterpret_cast<const bf16_t*>(dO),
+                     reinterpret_cast<const bf16_t*>(O), LSE, sinks, delta,
+                     lse2, partials, S, Hq, OStrides{o_sb, o_sh, o_sr});
+  VH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_attn_dsinks_finish, dim3((Hq + 63) / 64), dim3(64), 0,
+                     s, partials, dsinks, B, Hq, nblk);
+  VH_HIP(hipGetLastError());
+  return 0;
+}
+
 static int attn_bwd2_launch(const uint16_t* Q, const uint16_t* K,
                             const uint16_t* V, const uint16_t* dO,
                             const float* delta, const float* lse2,
                             uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B,
                             int Hq, int Hkv, int64_t S, float scale,
                             const int32_t* doc_start, const int32_t* doc_end,
-                            OStrides dos, void* stream) {
+                            OStrides dos, void* stream,
+                            bool shared_bounds = false) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   VH_CHECK(S % 128 == 0, "S %% 128 != 0");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
   VH_CHECK((doc_start == nullptr) == (doc_end == nullptr),
            "doc_start/doc_end must be passed together");
-  VH_CHECK(doc_start == nullptr || B == 1, "varlen requires packed B == 1");
+  VH_CHECK(doc_start == nullptr || B == 1 || shared_bounds,
+           "varlen requires packed B == 1");
   dim3 grid_kv((uint32_t)(S / 64), (uint32_t)(B * Hkv));
   dim3 grid_q((uint32_t)(S / 128), (uint32_t)(B * Hq));
   auto launch_dkv = [&](auto kern) {
@@ -1223,4 +1362,24 @@ extern "C" int vh_attn_bwd2_ostrided_bf16(
   return attn_bwd2_launch(Q, K, V, dO, delta, lse2, dQ, dK, dV, B, Hq, Hkv, S,
                           scale, doc_start, doc_end,
                           OStrides{do_sb, do_sh, do_sr}, stream);
+}
+
+/* vh_attn_bwd2_ostrided_bf16 with key-window bounds shared by the batch.
+ * lo / hi (nullable together): int32 [S]; lo[q] is the first key row q sees,
+ * hi[j] the exclusive end of the rows that see key j, both monotone
+ * non-decreasing with lo[q] <= q < hi[q] <= S; B > 1 allowed. delta and lse2
+ * come from vh_attn_bwd_pre_sink_bf16: with a sink-inclusive LSE the two
+ * kernels need nothing else for sinks. S % 256 == 0. */
+extern "C" int vh_attn_bwd2_win_bf16(
+    const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* dO,
+    const float* delta, const float* lse2, uint16_t* dQ, uint16_t* dK,
+    uint16_t* dV, int B, int Hq, int Hkv, int64_t S, float scale,
+    const int32_t* lo, const int32_t* hi, int64_t do_sb, int64_t do_sh,
+    int64_t do_sr, void* stream) {
+  VH_CHECK(S % 256 == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(scale > 0, "scale must be > 0 (got %g)", (double)scale);
+  if (int rc = check_ostrides(dO, do_sb, do_sh, do_sr)) return rc;
+  return attn_bwd2_launch(Q, K, V, dO, delta, lse2, dQ, dK, dV, B, Hq, Hkv, S,
+                          scale, lo, hi, OStrides{do_sb, do_sh, do_sr}, stream,
+                          /*shared_bounds=*/true);
 }

@@ -45,6 +45,16 @@ PRESETS = {
         num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
         head_dim=128, qk_norm=False,
     ),
+    # gpt-oss attention at test scale: alternating sliding / full layers, a
+    # 128-key window and attention sinks on D=128 heads (no q/k norm, as in
+    # gpt-oss)
+    "tiny-d128-swa": ModelConfig(
+        name="tiny-d128-swa", vocab_size=512, hidden_size=256, intermediate_size=512,
+        num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
+        head_dim=128, qk_norm=False, sliding_window=128,
+        layer_types=("sliding_attention", "full_attention"),
+        attention_sinks=True,
+    ),
     # qwen2-architecture knobs at test scale: attention bias on, no qk norm
     "tiny-qwen2": ModelConfig(
         name="tiny-qwen2", vocab_size=512, hidden_size=128, intermediate_size=256,

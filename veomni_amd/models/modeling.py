@@ -64,6 +64,15 @@ class ModelConfig:
     # clamped SwiGLU in the experts (gpt-oss / DeepSeek-V4): gate <= L,
     # -L <= up <= L before silu(gate) * up; None = plain SwiGLU
     swiglu_limit: Optional[float] = None
+    # sliding-window attention (Mistral / Qwen2 SWA, Gemma-3, gpt-oss): query
+    # i sees keys i-W+1 .. i. layer_types picks the layers that slide
+    # ("sliding_attention") and those that do not ("full_attention"), one
+    # entry per layer; None with a window means every layer slides
+    sliding_window: Optional[int] = None
+    layer_types: Optional[tuple] = None
+    # gpt-oss attention sinks: one learned logit per head that joins every
+    # row's softmax and carries no value
+    attention_sinks: bool = False
     # multimodal (Qwen2.5-VL) 3D-RoPE channel sections (t, h, w); None = 1D
     mrope_section: Optional[tuple] = None
     name: str = "model"
@@ -71,6 +80,26 @@ class ModelConfig:
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
+        from ..ops.kernels.attention import check_sliding_window
+
+        check_sliding_window(self.sliding_window)
+        if self.layer_types is not None:
+            self.layer_types = tuple(self.layer_types)
+            if len(self.layer_types) != self.num_hidden_layers or any(
+                    t not in ("full_attention", "sliding_attention")
+                    for t in self.layer_types):
+                raise ValueError(
+                    "layer_types needs one 'full_attention' / 'sliding_attention' "
+                    f"entry per layer, got {self.layer_types!r}")
+
+    def layer_sliding_window(self, layer_idx: int) -> Optional[int]:
+        """The window of layer layer_idx, None where it attends fully."""
+        if self.sliding_window is None:
+            return None
+        if self.layer_types is not None \
+                and self.layer_types[layer_idx] != "sliding_attention":
+            return None
+        return self.sliding_window
 
     @property
     def is_moe(self) -> bool:
@@ -155,13 +184,28 @@ def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
 
 
 def sdpa_attention(module, query, key, value, attention_mask, dropout=0.0,
-                   scaling=None, doc_start=None, **kwargs):
+                   scaling=None, doc_start=None, doc_end=None,
+                   sliding_window=None, s_aux=None, **kwargs):
     """Eager/SDPA attention on [B,h,S,D] (HF sdpa semantics). GQA repeat is
     derived from the shapes (under Ulysses the per-rank head counts differ
     from the module's config attrs). doc_start (int32 [S]) applies the
     packed-varlen block-diagonal causal mask (the reference flash-attn
     cu_seqlens semantics, attention/flash.py:61-91) as an explicit mask —
-    this is the eager oracle for the HIP varlen kernels."""
+    this is the eager oracle for the HIP varlen kernels. sliding_window and
+    s_aux ([h] attention-sink logits) take the explicit-mask + sink-column
+    form of the reference's gpt-oss eager_attention_forward."""
+    if sliding_window is not None or s_aux is not None:
+        from ..ops.kernels.attention import (eager_window_sink_attention,
+                                             window_bounds)
+
+        if scaling is None:
+            scaling = query.shape[-1] ** -0.5
+        lo, _ = window_bounds(query.shape[2], sliding_window, doc_start,
+                              doc_end, query.device)
+        out = eager_window_sink_attention(
+            query, key, value, scaling, lo, s_aux, dropout=dropout,
+            training=getattr(module, "training", False))
+        return out.transpose(1, 2).contiguous(), None
     n_rep = query.shape[1] // key.shape[1]
     key = repeat_kv(key, n_rep)
     value = repeat_kv(value, n_rep)
@@ -205,6 +249,24 @@ class Attention(nn.Module):
             self.k_norm = RMSNorm(self.head_dim, eps=config.rms_norm_eps)
         else:
             self.q_norm = self.k_norm = None
+        self.sliding_window = config.layer_sliding_window(layer_idx)
+        if config.attention_sinks:
+            self.sinks = nn.Parameter(torch.empty(self.num_heads))
+        else:
+            self.sinks = None
+
+    def _window_sink_kwargs(self, kwargs) -> dict:
+        """The layer's own sliding_window= / s_aux= next to the caller's
+        attention kwargs; nothing is added where the layer has neither, so
+        such layers call the slot exactly as before."""
+        if self.sliding_window is None and self.sinks is None:
+            return kwargs
+        kwargs = dict(kwargs)
+        if self.sliding_window is not None:
+            kwargs["sliding_window"] = self.sliding_window
+        if self.sinks is not None:
+            kwargs["s_aux"] = self.sinks
+        return kwargs
 
     # "fused": q/k norms on the qkv slices in place and token-major attention
     # output, where that applies (see _fused_layout_applies); "slots": always
@@ -224,7 +286,12 @@ class Attention(nn.Module):
     def forward(self, hidden_states, position_embeddings, **kwargs):
         input_shape = hidden_states.shape[:-1]
         ps = get_parallel_state()
+        kwargs = self._window_sink_kwargs(kwargs)
         if ps.ulysses_enabled and ps.async_ulysses:
+            if self.sliding_window is not None or self.sinks is not None:
+                raise NotImplementedError(
+                    "async Ulysses does not support sliding_window / "
+                    "attention_sinks; use the sync Ulysses path")
             # deepened async Ulysses (ref async_ulysses.py:48-419): the qkv
             # GEMM is split back into per-tensor launches on the comm path
             # so each all-to-all overlaps the next projection
@@ -306,6 +373,14 @@ class Attention(nn.Module):
                                       seq_dim=0, head_dim=1, group=group)
         vs = gather_seq_scatter_heads(v.squeeze(0).transpose(0, 1).contiguous(),
                                       seq_dim=0, head_dim=1, group=group)
+        if kwargs.get("s_aux") is not None:
+            # this rank's heads after the exchange (ref flash.py:249-255)
+            from ..ops.kernels.attention import slice_ulysses_sinks
+
+            kwargs = dict(kwargs)
+            kwargs["s_aux"] = slice_ulysses_sinks(
+                kwargs["s_aux"], query_head_count=q.shape[1],
+                local_query_head_count=qs.shape[1], group=group)
         out, _ = sdpa_attention(self, qs.transpose(0, 1)[None], ks.transpose(0, 1)[None],
                                 vs.transpose(0, 1)[None], None, dropout=0.0,
                                 scaling=self.scaling, **kwargs)  # [1, S, h/sp, D]

@@ -99,6 +99,13 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_attn_bwd2_ostrided_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_p, c_p, c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_i64, c_i64,
          c_i64, c_p)
+    _sig(lib, "vh_attn_fwd_win_sink_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int,
+         c_int, c_i64, c_f32, c_p, c_p, c_i64, c_i64, c_i64, c_p)
+    _sig(lib, "vh_attn_bwd_pre_sink_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_p, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_p)
+    _sig(lib, "vh_attn_bwd2_win_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_p, c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_i64, c_i64, c_i64,
+         c_p)
     _sig(lib, "vh_lbl_fwd", c_p, c_int, c_p, c_i64, c_int, c_int, c_p, c_int, c_p)
     _sig(lib, "vh_lbl_finish", c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_bwd", c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_p)
@@ -686,6 +693,96 @@ def attn_bwd_token_major(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             dptr(doc_end) if doc_end is not None else None,
             *strides, cur_stream()), "vh_attn_bwd2_ostrided")
     return dq, dk, dv
+
+
+def _check_window_sinks(B, Hq, S, D, device, lo, hi, sinks):
+    assert D == 128 and S % 256 == 0, (S, D)
+    for t in (lo, hi):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (S,)
+                             and t.is_contiguous() and t.device == device), \
+            "window bounds: int32 [S], contiguous, on the inputs' device"
+    assert sinks is None or (sinks.dtype == torch.float32
+                             and sinks.shape == (Hq,) and sinks.is_contiguous()
+                             and sinks.device == device), \
+        "sinks: fp32 [Hq], contiguous, on the inputs' device"
+
+
+def attn_fwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                      scale: float, lo: torch.Tensor | None = None,
+                      sinks: torch.Tensor | None = None,
+                      token_major: bool = False):
+    """attn_fwd / attn_fwd_token_major with a key window and attention sinks
+    (vh_attn_fwd_win_sink_bf16). lo: int32 [S] first visible key per row,
+    shared by the batch (ops.kernels.attention.window_bounds); sinks: fp32
+    [Hq] logits of the extra softmax column. Returns (o, lse); lse includes
+    the sink."""
+    B, Hq, S, D = q.shape
+    Hkv = k.shape[1]
+    _check_window_sinks(B, Hq, S, D, q.device, lo, None, sinks)
+    if token_major:
+        o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
+        strides = _bhs_strides(o.transpose(1, 2))
+    else:
+        o = torch.empty_like(q)
+        strides = _bhs_strides(o)
+    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+    with _prof("attn_fwd", 2.0 * 2 * S * S * Hq * D * 0.5 * B):
+        check(get_lib().vh_attn_fwd_win_sink_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(o), dptr(lse), B, Hq, Hkv, S, scale,
+            dptr(lo) if lo is not None else None,
+            dptr(sinks) if sinks is not None else None,
+            *strides, cur_stream()), "vh_attn_fwd_win_sink")
+    return o, lse
+
+
+def attn_bwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                      o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
+                      scale: float, lo: torch.Tensor | None = None,
+                      hi: torch.Tensor | None = None,
+                      sinks: torch.Tensor | None = None,
+                      token_major: bool = False):
+    """Backward for attn_fwd_win_sink. Returns head-major (dq, dk, dv) and
+    dsinks (fp32 [Hq], None without sinks). dsinks is summed in a fixed order
+    (no atomics): the same bits from run to run and for both layouts."""
+    B, Hq, S, D = q.shape
+    Hkv = k.shape[1]
+    _check_window_sinks(B, Hq, S, D, q.device, lo, hi, sinks)
+    assert (lo is None) == (hi is None)
+    if token_major:
+        assert o.shape == (B, S, Hq, D) and o.is_contiguous(), (o.shape, o.stride())
+        strides = _bhs_strides(o.transpose(1, 2))
+    else:
+        assert o.shape == (B, Hq, S, D) and o.is_contiguous(), (o.shape, o.stride())
+        strides = _bhs_strides(o)
+    assert do.shape == o.shape
+    do = do.contiguous()
+    rows = B * Hq * S
+    dev = q.device
+    delta = torch.empty(rows, dtype=torch.float32, device=dev)
+    lse2 = torch.empty(rows, dtype=torch.float32, device=dev)
+    dsinks = part = None
+    if sinks is not None:
+        dsinks = torch.empty(Hq, dtype=torch.float32, device=dev)
+        part = torch.empty(B * Hq * (S // 256), dtype=torch.float32, device=dev)
+    lib = get_lib()
+    with _prof("attn_bwd", 3.0 * 2 * 2 * S * S * Hq * D * 0.5 * B):
+        check(lib.vh_attn_bwd_pre_sink_bf16(
+            dptr(do), dptr(o), dptr(lse.contiguous()),
+            dptr(sinks) if sinks is not None else None,
+            dptr(delta), dptr(lse2),
+            dptr(dsinks) if dsinks is not None else None,
+            dptr(part) if part is not None else None,
+            B, Hq, S, *strides, cur_stream()), "vh_attn_bwd_pre_sink")
+        dq = torch.empty(B, Hq, S, D, dtype=torch.bfloat16, device=dev)
+        dk = torch.empty(B, Hkv, S, D, dtype=torch.bfloat16, device=dev)
+        dv = torch.empty(B, Hkv, S, D, dtype=torch.bfloat16, device=dev)
+        check(lib.vh_attn_bwd2_win_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(do), dptr(delta), dptr(lse2),
+            dptr(dq), dptr(dk), dptr(dv), B, Hq, Hkv, S, scale,
+            dptr(lo) if lo is not None else None,
+            dptr(hi) if hi is not None else None,
+            *strides, cur_stream()), "vh_attn_bwd2_win")
+    return dq, dk, dv, dsinks
 
 
 # ---------------------------------------------------- load-balancing loss

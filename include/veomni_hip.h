@@ -184,6 +184,62 @@ int vh_moe_silu_mul_clamp_weighted_bwd_bf16(const uint16_t* dy,
                                             int64_t rows, int64_t I, int has_w,
                                             float limit, void* stream);
 
+/* ---- gpt-oss experts (vh_moe_gpt_oss.hip) ------------------------------ */
+/* Streaming kernels around the grouped GEMMs of the gpt-oss expert bank
+ * (interleaved gate/up, per-expert biases, routing weight after down_proj).
+ * Replaces the per-expert loop of the reference's GptOssExperts.forward and
+ * the elementwise/bias-gradient steps of its fused gpt-oss expert function.
+ * Common: bf16 tensors, fp32 math. cumsum: int64 [G] inclusive row cumsum on
+ * the device; row r belongs to expert e iff cumsum[e-1] <= r < cumsum[e]
+ * (found on the device; empty experts are legal anywhere). I % 8 == 0,
+ * N % 8 == 0, rows >= 0 (rows == 0 returns at once except for the column
+ * sum, which still writes its zeros). */
+
+/* Forward GLU on the RAW fc1 (no bias in it), gate/up interleaved:
+ *   g_raw = fc1[r,2j] + bias[e,2j];   u_raw = fc1[r,2j+1] + bias[e,2j+1]
+ *   g = min(g_raw, L);  u = min(max(u_raw, -L), L)
+ *   out[r,j] = bf16((u + 1) * g * sigmoid(alpha * g))
+ * fc1 [rows, 2I], bias [G, 2I], out [rows, I]. limit: finite, > 0, already
+ * rounded to bf16 by the caller; alpha finite. */
+int vh_moe_gptoss_glu_bf16(const uint16_t* fc1, const uint16_t* bias,
+                           const int64_t* cumsum, uint16_t* out, int64_t rows,
+                           int64_t I, int G, float alpha, float limit,
+                           void* stream);
+
+/* Backward of the above from the same raw fc1 and bias (nothing else saved):
+ *   s  = sigmoid(alpha*g)
+ *   dg = g_raw <= L       ? dy*(u+1)*(s + alpha*g*s*(1-s)) : 0
+ *   du = -L <= u_raw <= L ? dy*g*s                          : 0
+ * dfc1 [rows, 2I] interleaved; inclusive bounds; NaN gets a zero gradient. */
+int vh_moe_gptoss_glu_bwd_bf16(const uint16_t* dy, const uint16_t* fc1,
+                               const uint16_t* bias, const int64_t* cumsum,
+                               uint16_t* dfc1, int64_t rows, int64_t I, int G,
+                               float alpha, float limit, void* stream);
+
+/* out[r,:] = bf16((x[r,:] + bias[e,:]) * w_row[r]); w_row NULL = factor 1.
+ * x, out [rows, N]; bias [G, N]; w_row bf16 [rows]. */
+int vh_moe_expert_bias_scale_bf16(const uint16_t* x, const uint16_t* bias,
+                                  const int64_t* cumsum, const uint16_t* w_row,
+                                  uint16_t* out, int64_t rows, int64_t N, int G,
+                                  void* stream);
+
+/* dx = bf16(dy * w_row[r]); dw_row[r] = sum_n (x + bias) * dy in fp32, stored
+ * (not accumulated: no zero fill needed). w_row NULL: dx = dy, dw_row
+ * untouched. */
+int vh_moe_expert_bias_scale_bwd_bf16(const uint16_t* dy, const uint16_t* x,
+                                      const uint16_t* bias,
+                                      const int64_t* cumsum,
+                                      const uint16_t* w_row, uint16_t* dx,
+                                      float* dw_row, int64_t rows, int64_t N,
+                                      int G, void* stream);
+
+/* out[g,n] = sum over the rows of expert g of x[r,n]; x bf16 [rows, N], out
+ * fp32 [G, N]. Every element is written (empty experts: exact zeros). Fixed
+ * summation order, no atomics: bit-reproducible. Serves both bias grads. */
+int vh_moe_segment_colsum_bf16(const uint16_t* x, const int64_t* cumsum,
+                               float* out, int64_t rows, int64_t N, int G,
+                               void* stream);
+
 /* ---- RMSNorm------------------------------------------------------------ */
 
 /* y = w * cast_bf16(x_f32 * rsqrt(mean(x^2)+eps)); saves rstd fp32 [T].

@@ -18,6 +18,7 @@ SOURCES = [
     "vh_abi.cpp",
     "vh_moe_ops.hip",
     "vh_moe_swiglu_limit.hip",
+    "vh_moe_gpt_oss.hip",
     "vh_group_gemm.hip",
     "vh_group_gemm8.hip",
     "vh_norms.hip",

@@ -67,6 +67,16 @@ PRESETS = {
         head_dim=32, qk_norm=True, num_experts=8, num_experts_per_tok=2,
         moe_intermediate_size=64, router_aux_loss_coef=0.001,
     ),
+    # tiny-moe's dimensions with the gpt-oss expert module: interleaved
+    # gate/up, expert and router biases, clamped (up + 1) * gate * sigmoid
+    # activation (no q/k norm, as in gpt-oss; full attention, no sinks)
+    "tiny-gpt-oss-moe": ModelConfig(
+        name="tiny-gpt-oss-moe", vocab_size=512, hidden_size=128, intermediate_size=256,
+        num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=2,
+        head_dim=32, qk_norm=False, num_experts=8, num_experts_per_tok=2,
+        moe_intermediate_size=64, router_aux_loss_coef=0.001,
+        expert_style="gpt_oss", swiglu_limit=7.0,
+    ),
 }
 
 # VLM presets (VLConfig: text + vision towers), built via build_vl_model

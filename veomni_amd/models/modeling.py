@@ -12,7 +12,8 @@ interoperate.
 
 OpSlots (bound by `bind_ops`, ref auto.py:63-107 `_bind_veomni_ops`):
   rms_norm/standard, rotary_pos_emb/full, swiglu_mlp/standard,
-  moe_experts/standard, cross_entropy_loss/causal, load_balancing_loss/standard
+  moe_experts/standard, moe_experts/gpt_oss (expert_style="gpt_oss"),
+  cross_entropy_loss/causal, load_balancing_loss/standard
 plus the attention interface (veomni_flash_attention_2_with_sp semantics) via
 `veomni_amd.ops.kernels.attention`.
 """
@@ -34,6 +35,7 @@ veomni_rms_norm = OpSlot("rms_norm", "standard")
 veomni_apply_rotary_pos_emb = OpSlot("rotary_pos_emb", "full")
 veomni_swiglu_mlp = OpSlot("swiglu_mlp", "standard")
 veomni_moe_experts_forward = OpSlot("moe_experts", "standard")
+veomni_gpt_oss_moe_experts_forward = OpSlot("moe_experts", "gpt_oss")
 veomni_causal_lm_loss = OpSlot("cross_entropy_loss", "causal")
 veomni_load_balancing_loss = OpSlot("load_balancing_loss", "standard")
 veomni_attention = OpSlot("attention", "sdpa_with_sp")
@@ -64,6 +66,12 @@ class ModelConfig:
     # clamped SwiGLU in the experts (gpt-oss / DeepSeek-V4): gate <= L,
     # -L <= up <= L before silu(gate) * up; None = plain SwiGLU
     swiglu_limit: Optional[float] = None
+    # expert module: "standard" = the Qwen3-MoE bank (Experts + TopKRouter),
+    # "gpt_oss" = GptOssExperts + GptOssTopKRouter (interleaved gate/up,
+    # biases, (up + 1) * gate * sigmoid(swiglu_alpha * gate) on the clamped
+    # values; always clamps, so it needs a swiglu_limit)
+    expert_style: str = "standard"
+    swiglu_alpha: float = 1.702
     # sliding-window attention (Mistral / Qwen2 SWA, Gemma-3, gpt-oss): query
     # i sees keys i-W+1 .. i. layer_types picks the layers that slide
     # ("sliding_attention") and those that do not ("full_attention"), one
@@ -83,6 +91,14 @@ class ModelConfig:
         from ..ops.kernels.attention import check_sliding_window
 
         check_sliding_window(self.sliding_window)
+        if self.expert_style not in ("standard", "gpt_oss"):
+            raise ValueError(
+                "expert_style must be 'standard' or 'gpt_oss', got "
+                f"{self.expert_style!r}")
+        if self.expert_style == "gpt_oss" and self.swiglu_limit is None:
+            raise ValueError(
+                "expert_style='gpt_oss' needs a swiglu_limit: these experts "
+                "always clamp (gpt-oss uses 7.0)")
         if self.layer_types is not None:
             self.layer_types = tuple(self.layer_types)
             if len(self.layer_types) != self.num_hidden_layers or any(
@@ -564,11 +580,115 @@ class Experts(nn.Module):
         return final
 
 
+def _gpt_oss_apply_gate(gate_up, alpha, limit):
+    """Interleaved clamped GLU of gpt-oss (ref GptOssExperts._apply_gate)."""
+    gate, up = gate_up[..., ::2], gate_up[..., 1::2]
+    gate = gate.clamp(min=None, max=limit)
+    up = up.clamp(min=-limit, max=limit)
+    glu = gate * torch.sigmoid(gate * alpha)
+    return (up + 1) * glu
+
+
+class _EagerEPGptOssExperts:
+    """Eager gpt-oss expert compute for the EP dispatch path (plain autograd
+    ops; routing weights applied later by unpermute)."""
+
+    @staticmethod
+    def apply(permute_tokens, cumsum, gate_up_w, gate_up_b, down_w, down_b,
+              alpha, limit):
+        outs = []
+        start = 0
+        for g in range(gate_up_w.shape[0]):
+            end = int(cumsum[g])
+            cur = permute_tokens[start:end]
+            gate_up = cur @ gate_up_w[g] + gate_up_b[g]
+            outs.append(_gpt_oss_apply_gate(gate_up, alpha, limit) @ down_w[g]
+                        + down_b[g])
+            start = end
+        return torch.cat(outs, dim=0)
+
+
+class GptOssExperts(nn.Module):
+    """gpt-oss expert bank (ref GptOssExperts): gate_up_proj [E,H,2I] with
+    gate / up interleaved along the last dim, down_proj [E,I,H], a bias on
+    each; routing weight applied after down_proj + bias."""
+
+    def __init__(self, config: ModelConfig):
+        super().__init__()
+        self.intermediate_size = config.moe_intermediate_size
+        self.num_experts = config.num_experts
+        self.hidden_size = config.hidden_size
+        E, H, I = self.num_experts, self.hidden_size, self.intermediate_size
+        self.gate_up_proj = nn.Parameter(torch.empty(E, H, 2 * I))
+        self.gate_up_proj_bias = nn.Parameter(torch.empty(E, 2 * I))
+        self.down_proj = nn.Parameter(torch.empty(E, I, H))
+        self.down_proj_bias = nn.Parameter(torch.empty(E, H))
+        self.alpha = config.swiglu_alpha
+        self.limit = config.swiglu_limit
+
+    def _apply_gate(self, gate_up: torch.Tensor) -> torch.Tensor:
+        return _gpt_oss_apply_gate(gate_up, self.alpha, self.limit)
+
+    def forward(self, hidden_states, router_indices=None, routing_weights=None):
+        if veomni_gpt_oss_moe_experts_forward.use_non_eager_impl:
+            return veomni_gpt_oss_moe_experts_forward(
+                self, hidden_states, router_indices, routing_weights)
+        if get_parallel_state().ep_enabled:
+            # eager under EP: the local bank holds E/ep experts, so the loop
+            # below cannot index it; go through dispatch / combine
+            from ..distributed.moe import dispatch_to_ep_class
+
+            return dispatch_to_ep_class(
+                _EagerEPGptOssExperts, self.num_experts, routing_weights,
+                router_indices, hidden_states, self.gate_up_proj,
+                self.gate_up_proj_bias, self.down_proj, self.down_proj_bias,
+                self.alpha, self.limit)
+        next_states = torch.zeros_like(hidden_states)
+        with torch.no_grad():
+            expert_mask = F.one_hot(router_indices, num_classes=self.num_experts)
+            expert_mask = expert_mask.permute(2, 1, 0)
+            expert_hit = torch.greater(expert_mask.sum(dim=(-1, -2)), 0).nonzero()
+        for expert_idx in expert_hit:
+            e = int(expert_idx[0])
+            top_k_pos, token_idx = torch.where(expert_mask[e])
+            cur = hidden_states[token_idx]
+            gate_up = cur @ self.gate_up_proj[e] + self.gate_up_proj_bias[e]
+            gated = self._apply_gate(gate_up)
+            out = gated @ self.down_proj[e] + self.down_proj_bias[e]
+            weighted = out * routing_weights[token_idx, top_k_pos, None]
+            next_states.index_add_(0, token_idx, weighted.to(hidden_states.dtype))
+        return next_states
+
+
+class GptOssTopKRouter(nn.Module):
+    """gpt-oss router (ref GptOssTopKRouter): biased linear, top-k on the
+    LOGITS, softmax over the k picked values in the logits' dtype."""
+
+    def __init__(self, config: ModelConfig):
+        super().__init__()
+        self.top_k = config.num_experts_per_tok
+        self.num_experts = config.num_experts
+        self.hidden_dim = config.hidden_size
+        self.weight = nn.Parameter(torch.zeros(self.num_experts, self.hidden_dim))
+        self.bias = nn.Parameter(torch.zeros(self.num_experts))
+
+    def forward(self, hidden_states):
+        hidden_states = hidden_states.reshape(-1, self.hidden_dim)
+        router_logits = F.linear(hidden_states, self.weight, self.bias)
+        top_v, top_i = torch.topk(router_logits, self.top_k, dim=-1)
+        scores = F.softmax(top_v, dim=1, dtype=top_v.dtype)
+        return router_logits, scores, top_i
+
+
 class SparseMoeBlock(nn.Module):
     def __init__(self, config: ModelConfig):
         super().__init__()
-        self.experts = Experts(config)
-        self.gate = TopKRouter(config)
+        if config.expert_style == "gpt_oss":
+            self.experts = GptOssExperts(config)
+            self.gate = GptOssTopKRouter(config)
+        else:
+            self.experts = Experts(config)
+            self.gate = TopKRouter(config)
 
     def forward(self, hidden_states):
         b, s, h = hidden_states.shape
@@ -654,15 +774,16 @@ class ForCausalLM(nn.Module):
     def get_parallel_plan(self):
         from ..distributed.parallel_plan import ParallelPlan
 
-        # Ref models/transformers/qwen3_moe/parallel_plan.py:6-16
-        return ParallelPlan(
-            extra_parallel_plan={
-                "ep": {
-                    "model.layers.*.mlp.experts.gate_up_proj": 0,
-                    "model.layers.*.mlp.experts.down_proj": 0,
-                }
-            }
-        )
+        # Ref models/transformers/qwen3_moe/parallel_plan.py:6-16 and, for
+        # the two expert biases, gpt_oss/parallel_plan.py
+        ep_plan = {
+            "model.layers.*.mlp.experts.gate_up_proj": 0,
+            "model.layers.*.mlp.experts.down_proj": 0,
+        }
+        if self.config.expert_style == "gpt_oss":
+            ep_plan["model.layers.*.mlp.experts.gate_up_proj_bias"] = 0
+            ep_plan["model.layers.*.mlp.experts.down_proj_bias"] = 0
+        return ParallelPlan(extra_parallel_plan={"ep": ep_plan})
 
     @torch.no_grad()
     def reset_parameters(self, seed: int = 1234):
@@ -683,7 +804,8 @@ class ForCausalLM(nn.Module):
         for name, p in sorted(self.named_parameters(), key=lambda kv: kv[0]):
             if name.endswith("layernorm.weight") or name.endswith("norm.weight") or ".q_norm" in name or ".k_norm" in name:
                 p.fill_(1.0)
-            elif name.endswith(".bias"):
+            elif name.endswith(".bias") or name.endswith("_bias"):
+                # incl. the gpt-oss experts' *_proj_bias (HF _init_weights)
                 p.zero_()
             else:
                 buf = torch.empty(p.shape, dtype=torch.float32, device=dev)
@@ -837,3 +959,6 @@ def bind_ops(impl: str | dict = "eager") -> None:
     for op_name, slot in slots.items():
         name = impl if isinstance(impl, str) else impl.get(op_name, "eager")
         slot.bind(name)
+    # both expert variants follow the one "moe_experts" entry
+    veomni_gpt_oss_moe_experts_forward.bind(
+        impl if isinstance(impl, str) else impl.get("moe_experts", "eager"))

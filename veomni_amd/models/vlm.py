@@ -385,7 +385,7 @@ class VLForCausalLM(ForCausalLM):
                     or name.endswith("norm1.weight") or name.endswith("norm2.weight")
                     or name.endswith("ln_q.weight")):
                 p.fill_(1.0)
-            elif name.endswith(".bias"):
+            elif name.endswith(".bias") or name.endswith("_bias"):
                 p.zero_()
             else:
                 buf = torch.empty(p.shape, dtype=torch.float32, device=dev)

@@ -65,6 +65,16 @@ def get_lib() -> ctypes.CDLL:
          c_int, c_f32, c_p)
     _sig(lib, "vh_moe_silu_mul_clamp_weighted_bwd_bf16", c_p, c_p, c_p, c_p, c_p,
          c_i64, c_i64, c_int, c_f32, c_p)
+    _sig(lib, "vh_moe_gptoss_glu_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64, c_int,
+         c_f32, c_f32, c_p)
+    _sig(lib, "vh_moe_gptoss_glu_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_i64,
+         c_i64, c_int, c_f32, c_f32, c_p)
+    _sig(lib, "vh_moe_expert_bias_scale_bf16", c_p, c_p, c_p, c_p, c_p, c_i64,
+         c_i64, c_int, c_p)
+    _sig(lib, "vh_moe_expert_bias_scale_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p,
+         c_p, c_i64, c_i64, c_int, c_p)
+    _sig(lib, "vh_moe_segment_colsum_bf16", c_p, c_p, c_p, c_i64, c_i64, c_int,
+         c_p)
     _sig(lib, "vh_rmsnorm_fwd_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p)
     _sig(lib, "vh_rmsnorm_bwd_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p)
     _sig(lib, "vh_rmsnorm128_fwd_strided_bf16", c_p, c_p, c_p, c_p, c_i64, c_i64,
@@ -329,6 +339,107 @@ def silu_mul_weighted_bwd(dy: torch.Tensor, fc1: torch.Tensor,
         dptr(dw_row) if has_w else None, rows, I, int(has_w), cur_stream()),
         "vh_moe_silu_mul_weighted_bwd")
     return dfc1, dw_row
+
+
+# ---- gpt-oss experts (vh_moe_gpt_oss.hip) ----------------------------------
+def _cumsum_i64(cumsum: torch.Tensor, G: int | None = None) -> torch.Tensor:
+    assert G is None or cumsum.numel() == G, (cumsum.shape, G)
+    return cumsum.to(torch.int64).contiguous()
+
+
+def gptoss_glu(fc1: torch.Tensor, bias: torch.Tensor, cumsum: torch.Tensor,
+               alpha: float, limit: float) -> torch.Tensor:
+    """(up + 1) * gate * sigmoid(alpha * gate) on the clamped, biased,
+    INTERLEAVED pre-activation: fc1 [rows, 2I] is the raw grouped-GEMM output,
+    bias [G, 2I] is added per expert in the kernel (L = bf16(limit))."""
+    assert fc1.dtype == torch.bfloat16 and bias.dtype == torch.bfloat16
+    rows, twoI = fc1.shape
+    I = twoI // 2
+    assert bias.shape[1] == twoI, (fc1.shape, bias.shape)
+    G = bias.shape[0]
+    out = torch.empty(rows, I, dtype=fc1.dtype, device=fc1.device)
+    with _prof("gptoss_glu", 2.0 * rows * 3 * I):
+        check(get_lib().vh_moe_gptoss_glu_bf16(
+            dptr(fc1.contiguous()), dptr(bias.contiguous()),
+            dptr(_cumsum_i64(cumsum, G)), dptr(out), rows, I, G, float(alpha),
+            swiglu_limit_bf16(limit), cur_stream()), "vh_moe_gptoss_glu")
+    return out
+
+
+def gptoss_glu_bwd(dy: torch.Tensor, fc1: torch.Tensor, bias: torch.Tensor,
+                   cumsum: torch.Tensor, alpha: float,
+                   limit: float) -> torch.Tensor:
+    """dfc1 [rows, 2I] (interleaved) of gptoss_glu, recomputed from the raw
+    fc1 and the bias; zero outside the inclusive clamp bounds."""
+    assert fc1.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16
+    rows, twoI = fc1.shape
+    I = twoI // 2
+    assert dy.shape == (rows, I) and bias.shape[1] == twoI
+    G = bias.shape[0]
+    dfc1 = torch.empty_like(fc1)
+    with _prof("gptoss_glu_bwd", 2.0 * rows * 5 * I):
+        check(get_lib().vh_moe_gptoss_glu_bwd_bf16(
+            dptr(dy.contiguous()), dptr(fc1.contiguous()),
+            dptr(bias.contiguous()), dptr(_cumsum_i64(cumsum, G)), dptr(dfc1), rows,
+            I, G, float(alpha), swiglu_limit_bf16(limit), cur_stream()),
+            "vh_moe_gptoss_glu_bwd")
+    return dfc1
+
+
+def expert_bias_scale(x: torch.Tensor, bias: torch.Tensor, cumsum: torch.Tensor,
+                      w_row: torch.Tensor | None) -> torch.Tensor:
+    """(x[r] + bias[expert(r)]) * w_row[r]; w_row None is a factor of 1."""
+    assert x.dtype == torch.bfloat16 and bias.dtype == torch.bfloat16
+    rows, N = x.shape
+    assert bias.shape[1] == N, (x.shape, bias.shape)
+    if w_row is not None:
+        assert w_row.dtype == torch.bfloat16 and w_row.numel() == rows
+    out = torch.empty_like(x)
+    with _prof("expert_bias_scale", 2.0 * rows * 2 * N):
+        check(get_lib().vh_moe_expert_bias_scale_bf16(
+            dptr(x.contiguous()), dptr(bias.contiguous()),
+            dptr(_cumsum_i64(cumsum, bias.shape[0])),
+            dptr(w_row.contiguous()) if w_row is not None else None, dptr(out),
+            rows, N, bias.shape[0], cur_stream()), "vh_moe_expert_bias_scale")
+    return out
+
+
+def expert_bias_scale_bwd(dy: torch.Tensor, x: torch.Tensor, bias: torch.Tensor,
+                          cumsum: torch.Tensor, w_row: torch.Tensor | None):
+    """(dx, dw_row) of expert_bias_scale: dx = dy * w_row[r] and
+    dw_row[r] = sum_n (x + bias) * dy (fp32, stored by the kernel, so the
+    buffer is allocated uninitialised). w_row None: (a copy of dy, None)."""
+    assert dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+    rows, N = x.shape
+    assert dy.shape == x.shape and bias.shape[1] == N
+    has_w = w_row is not None
+    dx = torch.empty_like(x)
+    dw_row = torch.empty(rows, dtype=torch.float32, device=x.device) if has_w else None
+    with _prof("expert_bias_scale_bwd", 2.0 * rows * 3 * N):
+        check(get_lib().vh_moe_expert_bias_scale_bwd_bf16(
+            dptr(dy.contiguous()), dptr(x.contiguous()), dptr(bias.contiguous()),
+            dptr(_cumsum_i64(cumsum, bias.shape[0])),
+            dptr(w_row.contiguous()) if has_w else None, dptr(dx),
+            dptr(dw_row) if has_w else None, rows, N, bias.shape[0],
+            cur_stream()), "vh_moe_expert_bias_scale_bwd")
+    return dx, dw_row
+
+
+def segment_colsum(x: torch.Tensor, cumsum: torch.Tensor,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 [G, N] column sums of x [rows, N] over each expert's row segment;
+    fixed summation order (bit-reproducible), every element written."""
+    assert x.dtype == torch.bfloat16
+    rows, N = x.shape
+    G = cumsum.numel()
+    if out is None:
+        out = torch.empty(G, N, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == (G, N) and out.is_contiguous()
+    with _prof("segment_colsum", 2.0 * rows * N):
+        check(get_lib().vh_moe_segment_colsum_bf16(
+            dptr(x.contiguous()), dptr(_cumsum_i64(cumsum)), dptr(out), rows, N,
+            G, cur_stream()), "vh_moe_segment_colsum")
+    return out
 
 
 def rmsnorm_fwd(x: torch.Tensor, w: torch.Tensor, eps: float):

@@ -20,6 +20,13 @@ which then runs vh_moe_silu_mul_clamp_weighted(_bwd). The saved tensor is
 still the RAW fc1 — clamp and gradient mask are recomputed in the backward
 kernel, nothing extra is saved. With limit None every path issues exactly the
 calls it issued before the limit existed.
+
+gpt-oss experts (OpSlot moe_experts/gpt_oss; ref GptOssExperts and its fused
+gpt-oss expert function): a second provider further down, for the module
+with interleaved gate/up, per-expert biases and the routing weight after
+down_proj. Same grouped GEMMs on the stored [E,H,2I] / [E,I,H] layouts, with
+vh_moe_gptoss_glu(_bwd) / vh_moe_expert_bias_scale(_bwd) /
+vh_moe_segment_colsum around them.
 """
 
 from __future__ import annotations
@@ -236,6 +243,198 @@ def hip_fused_moe_forward(num_experts, routing_weights, selected_experts,
     return out.reshape(hidden_states.shape)
 
 
+# ---- gpt-oss experts (OpSlot moe_experts/gpt_oss) ------------------------
+# A different module from the bank above (ref GptOssExperts): gate_up_proj
+# [E, H, 2I] with gate / up INTERLEAVED along the last dim, down_proj
+# [E, I, H], per-expert biases on both, (up + 1) * gate * sigmoid(alpha *
+# gate) on the clamped values, routing weight applied AFTER down_proj + bias.
+# Both weights are [G, K, N] for their forward GEMM, so every GEMM below reads
+# them as they are stored (trans_b=False forward, True for the dgrads) and
+# the wgrad kernel writes [G, M, N] = their stored layout: no weight copies.
+# The grouped GEMMs produce RAW products; the kernels of vh_moe_gpt_oss.hip
+# add the biases, so the saved fc1 / fc2 are bias-free and the backward
+# recomputes clamp and mask from them (parity: the reference's
+# GptOssQuackFusedMoeExpertFunction, quack_gemm_interleave_gate_up.py).
+
+GPT_OSS_ALPHA = 1.702
+GPT_OSS_LIMIT = 7.0
+
+
+def _bias_grad(d_rows, cumsum, like):
+    """Per-expert bias gradient: fp32 segment column sum, cast to the
+    parameter's dtype."""
+    return hip_lib.segment_colsum(d_rows, cumsum).to(like.dtype)
+
+
+class HipGptOssFusedMoeFunction(torch.autograd.Function):
+    """Non-EP gpt-oss experts. The row-to-expert lookup happens on the device
+    (cumsum search in the kernels): no host read of the splits."""
+
+    @staticmethod
+    def forward(ctx, num_experts, gate_weights, expert_index, hidden_states,
+                gate_up_proj, gate_up_proj_bias, down_proj, down_proj_bias,
+                alpha, limit):
+        splits = hip_lib.expert_histogram(expert_index, num_experts)
+        _, scatter_index = compute_expert_scatter_index(expert_index)
+        x_s = hip_lib.moe_scatter(hidden_states, scatter_index)
+        cumsum_t = torch.cumsum(splits, dim=0)
+
+        fc1 = hip_lib.group_gemm_nk(x_s, gate_up_proj, cumsum_t, trans_b=False)
+        act = hip_lib.gptoss_glu(fc1, gate_up_proj_bias, cumsum_t, alpha, limit)
+        fc2 = hip_lib.group_gemm_nk(act, down_proj, cumsum_t, trans_b=False)
+
+        w = gate_weights.reshape(-1)
+        scattered_w = torch.empty_like(w)
+        scattered_w[scatter_index.flatten().to(torch.int64)] = w
+        y = hip_lib.expert_bias_scale(fc2, down_proj_bias, cumsum_t, scattered_w)
+        out = hip_lib.moe_gather(y, scatter_index)
+
+        ctx.alpha, ctx.limit = alpha, limit
+        ctx.save_for_backward(gate_weights, gate_up_proj, gate_up_proj_bias,
+                              down_proj, down_proj_bias, scatter_index,
+                              cumsum_t, x_s, fc1, act, fc2, scattered_w)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (gate_weights, gate_up_proj, gate_up_proj_bias, down_proj,
+         down_proj_bias, scatter_index, cumsum_t, x_s, fc1, act, fc2,
+         scattered_w) = ctx.saved_tensors
+        G = down_proj.shape[0]
+        grad_output = grad_output.view(-1, grad_output.shape[-1]).contiguous()
+
+        dy_rows = hip_lib.moe_scatter(grad_output, scatter_index)
+        d_fc2, dw_rows = hip_lib.expert_bias_scale_bwd(
+            dy_rows, fc2, down_proj_bias, cumsum_t, scattered_w)
+        grad_gate = dw_rows[scatter_index.flatten().to(torch.int64)]
+        grad_gate = grad_gate.reshape(gate_weights.shape).to(gate_weights.dtype)
+        d_down_bias = _bias_grad(d_fc2, cumsum_t, down_proj_bias)
+
+        d_act = hip_lib.group_gemm_nk(d_fc2, down_proj, cumsum_t, trans_b=True)
+        d_down = hip_lib.group_gemm_mn(act, d_fc2, cumsum_t, G)          # [G, I, H]
+
+        d_fc1 = hip_lib.gptoss_glu_bwd(d_act, fc1, gate_up_proj_bias, cumsum_t,
+                                       ctx.alpha, ctx.limit)
+        d_gate_up_bias = _bias_grad(d_fc1, cumsum_t, gate_up_proj_bias)
+        d_x_s = hip_lib.group_gemm_nk(d_fc1, gate_up_proj, cumsum_t, trans_b=True)
+        d_gate_up = hip_lib.group_gemm_mn(x_s, d_fc1, cumsum_t, G)       # [G, H, 2I]
+
+        grad_hidden = hip_lib.moe_gather(d_x_s, scatter_index)
+        return (None, grad_gate, None, grad_hidden, d_gate_up, d_gate_up_bias,
+                d_down, d_down_bias, None, None)
+
+
+def _gpt_oss_ep_fwd(tokens, cumsum, gate_up_proj, gate_up_proj_bias, down_proj,
+                    down_proj_bias, *, alpha, limit):
+    fc1 = hip_lib.group_gemm_nk(tokens, gate_up_proj, cumsum, trans_b=False)
+    act = hip_lib.gptoss_glu(fc1, gate_up_proj_bias, cumsum, alpha, limit)
+    fc2 = hip_lib.group_gemm_nk(act, down_proj, cumsum, trans_b=False)
+    # routing weights are applied later by tokens_post_all2all's unpermute
+    y = hip_lib.expert_bias_scale(fc2, down_proj_bias, cumsum, None)
+    return y, (tokens, gate_up_proj, gate_up_proj_bias, down_proj,
+               down_proj_bias, fc1, act)
+
+
+def _gpt_oss_ep_bwd_dgrad(dY, cumsum, saved, *, alpha, limit):
+    _, gate_up_proj, gate_up_proj_bias, down_proj, _, fc1, _ = saved
+    # w_row=None forward: d_fc2 is dY itself
+    d_act = hip_lib.group_gemm_nk(dY, down_proj, cumsum, trans_b=True)
+    d_fc1 = hip_lib.gptoss_glu_bwd(d_act, fc1, gate_up_proj_bias, cumsum,
+                                   alpha, limit)
+    d_tokens = hip_lib.group_gemm_nk(d_fc1, gate_up_proj, cumsum, trans_b=True)
+    return d_tokens, (dY, d_fc1)
+
+
+def _gpt_oss_ep_bwd_wgrad(cumsum, saved, stash):
+    tokens, _, gate_up_proj_bias, down_proj, down_proj_bias, _, act = saved
+    dY, d_fc1 = stash
+    G = down_proj.shape[0]
+    d_gate_up = hip_lib.group_gemm_mn(tokens, d_fc1, cumsum, G)
+    d_gate_up_bias = _bias_grad(d_fc1, cumsum, gate_up_proj_bias)
+    d_down = hip_lib.group_gemm_mn(act, dY, cumsum, G)
+    d_down_bias = _bias_grad(dY, cumsum, down_proj_bias)
+    return (d_gate_up, d_gate_up_bias, d_down, d_down_bias)
+
+
+@functools.lru_cache(maxsize=None)
+def gpt_oss_ep_a2a_class(alpha=GPT_OSS_ALPHA, limit=GPT_OSS_LIMIT):
+    """The overlapped gpt-oss EP class (weights: gate_up_proj,
+    gate_up_proj_bias, down_proj, down_proj_bias), built once per
+    (alpha, limit). Both bias column sums run in the wgrad leg, under the
+    return all-to-all."""
+    from ...distributed.moe import make_ep_a2a_class
+
+    alpha, limit = float(alpha), float(limit)
+    return make_ep_a2a_class(
+        functools.partial(_gpt_oss_ep_fwd, alpha=alpha, limit=limit),
+        functools.partial(_gpt_oss_ep_bwd_dgrad, alpha=alpha, limit=limit),
+        _gpt_oss_ep_bwd_wgrad)
+
+
+def check_gpt_oss_args(hidden_size, gate_up_proj, gate_up_proj_bias, down_proj,
+                       down_proj_bias, alpha, limit):
+    """Validate the gpt-oss expert arguments; returns (alpha, limit) as
+    floats. ValueError on a bad limit / alpha or on shapes that do not fit
+    [E,H,2I] / [E,2I] / [E,I,H] / [E,H]."""
+    if limit is None:
+        raise ValueError("swiglu_limit must be a finite number > 0 for the "
+                         "gpt-oss experts (they always clamp), got None")
+    limit = check_swiglu_limit(limit)
+    try:
+        ok = not isinstance(alpha, bool) and math.isfinite(alpha)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"alpha must be a finite number, got {alpha!r}")
+    if gate_up_proj.dim() != 3 or down_proj.dim() != 3:
+        raise ValueError(
+            "gate_up_proj must be [E, H, 2I] and down_proj [E, I, H], got "
+            f"{tuple(gate_up_proj.shape)} and {tuple(down_proj.shape)}")
+    E, H, twoI = gate_up_proj.shape
+    want = {"gate_up_proj": (E, hidden_size, twoI),
+            "gate_up_proj_bias": (E, twoI),
+            "down_proj": (E, twoI // 2, H),
+            "down_proj_bias": (E, H)}
+    got = {"gate_up_proj": gate_up_proj, "gate_up_proj_bias": gate_up_proj_bias,
+           "down_proj": down_proj, "down_proj_bias": down_proj_bias}
+    if twoI % 2:
+        raise ValueError(f"gate_up_proj last dim must be even (2I), got {twoI}")
+    for name, shape in want.items():
+        if tuple(got[name].shape) != shape:
+            raise ValueError(
+                f"{name} must be {list(shape)} ([E,H,2I] / [E,2I] / [E,I,H] / "
+                f"[E,H] layout), got {list(got[name].shape)}")
+    return float(alpha), limit
+
+
+def hip_gpt_oss_fused_moe_forward(num_experts, routing_weights, selected_experts,
+                                  hidden_states, gate_up_proj, gate_up_proj_bias,
+                                  down_proj, down_proj_bias,
+                                  alpha=GPT_OSS_ALPHA, limit=GPT_OSS_LIMIT):
+    """Signature parity: the reference's quack_gemm_gpt_oss_fused_moe_forward.
+    Everything is validated here, before any device work."""
+    alpha, limit = check_gpt_oss_args(
+        hidden_states.shape[-1], gate_up_proj, gate_up_proj_bias, down_proj,
+        down_proj_bias, alpha, limit)
+    hs = hidden_states.reshape(-1, hidden_states.shape[-1])
+    if get_parallel_state().ep_enabled:
+        from ...distributed.moe import dispatch_to_ep_a2a_class
+
+        out = dispatch_to_ep_a2a_class(
+            gpt_oss_ep_a2a_class(alpha, limit), num_experts, routing_weights,
+            selected_experts, hs, gate_up_proj, gate_up_proj_bias, down_proj,
+            down_proj_bias)
+    else:
+        if gate_up_proj.shape[0] != num_experts:
+            raise ValueError(
+                f"gate_up_proj holds {gate_up_proj.shape[0]} experts, "
+                f"num_experts is {num_experts}")
+        out = HipGptOssFusedMoeFunction.apply(
+            num_experts, routing_weights, selected_experts, hs, gate_up_proj,
+            gate_up_proj_bias, down_proj, down_proj_bias, alpha, limit)
+    return out.reshape(hidden_states.shape)
+
+
 def fused_moe_forward(num_experts, routing_weights, selected_experts,
                       hidden_states, fc1_1_weight, fc1_2_weight, fc2_weight,
                       fc1_1_2_weight=None, swiglu_limit=None):
@@ -289,5 +488,42 @@ KERNEL_REGISTRY.register(
         factory=_hip_moe_experts_factory,
         hardware=HardwareRequirement(device_type="gpu"),
         description="gfx950 grouped-GEMM fused MoE (vh_group_gemm_*)",
+    )
+)
+
+
+def _make_gpt_oss_moe_experts_adapter(raw_forward):
+    """OpSlot adapter for the gpt-oss experts module: pull num_experts, the
+    two weights, the two biases, alpha and limit off it."""
+
+    def adapter(self, hidden_states, router_indices, routing_weights):
+        return raw_forward(
+            num_experts=self.num_experts,
+            routing_weights=routing_weights.to(hidden_states.dtype),
+            selected_experts=router_indices,
+            hidden_states=hidden_states,
+            gate_up_proj=self.gate_up_proj,
+            gate_up_proj_bias=self.gate_up_proj_bias,
+            down_proj=self.down_proj,
+            down_proj_bias=self.down_proj_bias,
+            alpha=self.alpha,
+            limit=self.limit,
+        )
+
+    return adapter
+
+
+def _hip_gpt_oss_moe_experts_factory():
+    return _make_gpt_oss_moe_experts_adapter(hip_gpt_oss_fused_moe_forward)
+
+
+KERNEL_REGISTRY.register(
+    KernelSpec(
+        name="hip", op_name="moe_experts", variant="gpt_oss",
+        factory=_hip_gpt_oss_moe_experts_factory,
+        hardware=HardwareRequirement(device_type="gpu"),
+        description="gfx950 gpt-oss experts: grouped GEMMs on the stored "
+                    "layouts + vh_moe_gptoss_* / vh_moe_expert_bias_scale / "
+                    "vh_moe_segment_colsum",
     )
 )

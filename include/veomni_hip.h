@@ -407,6 +407,33 @@ int vh_attn_bwd2_win_bf16(const uint16_t* Q, const uint16_t* K,
                           const int32_t* hi, int64_t do_sb, int64_t do_sh,
                           int64_t do_sr, void* stream);
 
+/* Head dim 64 (csrc/vh_attention64.hip): the flash pair above for
+ * D = 64, head-major [B,H,S,64] bf16 everywhere, with the lo / hi / sinks
+ * contract of the *_win_sink calls (lo, hi, sinks nullable; lo and hi int32
+ * [S], monotone, shared by every batch row, so document bounds need B == 1,
+ * which the caller enforces; sinks fp32 [Hq], LSE includes the sink).
+ * fwd: O, LSE [B,Hq,S] fp32. bwd_pre: delta, lse2 = LSE*log2e [B*Hq*S] and,
+ * with sinks, dsinks [Hq] through partials (fp32 [B*Hq*S/256] workspace),
+ * summed in a fixed order without atomics. bwd2: dQ [B,Hq,S,64], dK / dV
+ * [B,Hkv,S,64], each written once; lo and hi both or neither.
+ * All three: S % 256 == 0; fwd and bwd2: scale > 0, Hq % Hkv == 0. */
+int vh_attn64_fwd_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
+                       uint16_t* O, float* LSE, int B, int Hq, int Hkv,
+                       int64_t S, float scale, const int32_t* lo,
+                       const float* sinks, void* stream);
+
+int vh_attn64_bwd_pre_bf16(const uint16_t* dO, const uint16_t* O,
+                           const float* LSE, const float* sinks, float* delta,
+                           float* lse2, float* dsinks, float* partials, int B,
+                           int Hq, int64_t S, void* stream);
+
+int vh_attn64_bwd2_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
+                        const uint16_t* dO, const float* delta,
+                        const float* lse2, uint16_t* dQ, uint16_t* dK,
+                        uint16_t* dV, int B, int Hq, int Hkv, int64_t S,
+                        float scale, const int32_t* lo, const int32_t* hi,
+                        void* stream);
+
 /* ---- Fused optimizer ----------------------------------------------------- */
 
 /* One-sweep AdamW over a device pointer table (torch semantics: decoupled

@@ -9,10 +9,20 @@ GPU box by gpurun (built artefacts travel with the snapshot).
 import os
 import subprocess
 import sys
+import tempfile
 
 CSRC = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(CSRC)
 OUT = os.path.join(PKG, "libveomni_hip.so")
+
+# Sources compiled on their own with extra flags and linked in as objects
+# (the other sources keep the one-command build and its code generation).
+# vh_attention64.hip: no packed-fp32 VALU forms (v_pk_mul_f32 and friends) in
+# the softmax stream.
+EXTRA_FLAGS = {
+    "vh_attention64.hip": ["-Xclang", "-target-feature", "-Xclang",
+                           "-packed-fp32-ops"],
+}
 
 SOURCES = [
     "vh_abi.cpp",
@@ -23,6 +33,7 @@ SOURCES = [
     "vh_group_gemm8.hip",
     "vh_norms.hip",
     "vh_attention.hip",
+    "vh_attention64.hip",
     "vh_ce.hip",
     "vh_logprob.hip",
     "vh_adamw.hip",
@@ -39,15 +50,25 @@ def build(verbose: bool = True) -> str:
         if verbose:
             print(f"[vh build] up to date: {OUT}")
         return OUT
-    cmd = [
-        "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-        "-shared", "-x", "hip",
-        *srcs,
-        "-o", OUT,
-    ]
-    if verbose:
-        print("[vh build]", " ".join(cmd))
-    subprocess.run(cmd, check=True)
+    base = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+    objs = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, flags in EXTRA_FLAGS.items():
+            obj = os.path.join(tmp, name + ".o")
+            cmd = [*base, *flags, "-c", "-x", "hip", os.path.join(CSRC, name),
+                   "-o", obj]
+            if verbose:
+                print("[vh build]", " ".join(cmd))
+            subprocess.run(cmd, check=True)
+            objs.append(obj)
+        cmd = [
+            *base, "-shared", *objs, "-x", "hip",
+            *[s for s in srcs if os.path.basename(s) not in EXTRA_FLAGS],
+            "-o", OUT,
+        ]
+        if verbose:
+            print("[vh build]", " ".join(cmd))
+        subprocess.run(cmd, check=True)
     return OUT
 
 

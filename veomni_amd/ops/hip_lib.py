@@ -116,6 +116,12 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_attn_bwd2_win_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_p, c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_i64, c_i64, c_i64,
          c_p)
+    _sig(lib, "vh_attn64_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int,
+         c_i64, c_f32, c_p, c_p, c_p)
+    _sig(lib, "vh_attn64_bwd_pre_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_int, c_int, c_i64, c_p)
+    _sig(lib, "vh_attn64_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_fwd", c_p, c_int, c_p, c_i64, c_int, c_int, c_p, c_int, c_p)
     _sig(lib, "vh_lbl_finish", c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_bwd", c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_p)
@@ -893,6 +899,88 @@ def attn_bwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             dptr(lo) if lo is not None else None,
             dptr(hi) if hi is not None else None,
             *strides, cur_stream()), "vh_attn_bwd2_win")
+    return dq, dk, dv, dsinks
+
+
+def _check_attn64(q, k, v, lo, hi, sinks):
+    B, Hq, S, D = q.shape
+    assert D == 64 and S % 256 == 0, (S, D)
+    assert k.shape == v.shape and k.shape[0] == B and k.shape[2:] == (S, D) \
+        and Hq % k.shape[1] == 0, (q.shape, k.shape, v.shape)
+    for t in (q, k, v):
+        assert t.dtype == torch.bfloat16 and t.is_contiguous() \
+            and t.device == q.device and q.is_cuda, \
+            "q/k/v: bf16, contiguous [B,H,S,64], on one GPU"
+    for t in (lo, hi):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (S,)
+                             and t.is_contiguous() and t.device == q.device), \
+            "bounds: int32 [S], contiguous, on the inputs' device"
+    assert sinks is None or (sinks.dtype == torch.float32
+                             and sinks.shape == (Hq,) and sinks.is_contiguous()
+                             and sinks.device == q.device), \
+        "sinks: fp32 [Hq], contiguous, on the inputs' device"
+
+
+def attn64_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+               lo: torch.Tensor | None = None,
+               sinks: torch.Tensor | None = None):
+    """Causal GQA flash attention forward at head_dim 64 (vh_attn64_fwd_bf16):
+    q [B,Hq,S,64] bf16 contiguous, k/v [B,Hkv,S,64]. lo: int32 [S] first
+    visible key per row (document and/or window bounds, shared by the batch);
+    sinks: fp32 [Hq]. Returns (o [B,Hq,S,64], lse [B,Hq,S], sink included)."""
+    _check_attn64(q, k, v, lo, None, sinks)
+    B, Hq, S, D = q.shape
+    o = torch.empty_like(q)
+    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+    with _prof("attn_fwd", 2.0 * 2 * S * S * Hq * D * 0.5 * B):
+        check(get_lib().vh_attn64_fwd_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(o), dptr(lse), B, Hq, k.shape[1], S,
+            scale, dptr(lo) if lo is not None else None,
+            dptr(sinks) if sinks is not None else None,
+            cur_stream()), "vh_attn64_fwd")
+    return o, lse
+
+
+def attn64_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+               o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
+               scale: float, lo: torch.Tensor | None = None,
+               hi: torch.Tensor | None = None,
+               sinks: torch.Tensor | None = None):
+    """Backward for attn64_fwd. Returns (dq [B,Hq,S,64], dk, dv [B,Hkv,S,64],
+    dsinks fp32 [Hq] or None); dsinks is summed in a fixed order, the same
+    bits from run to run."""
+    _check_attn64(q, k, v, lo, hi, sinks)
+    B, Hq, S, D = q.shape
+    Hkv = k.shape[1]
+    assert (lo is None) == (hi is None)
+    assert o.shape == q.shape and o.is_contiguous() and o.dtype == q.dtype
+    assert do.shape == q.shape and do.dtype == q.dtype, (do.shape, do.dtype)
+    assert lse.shape == (B, Hq, S) and lse.dtype == torch.float32
+    do = do.contiguous()
+    dev = q.device
+    delta = torch.empty(B * Hq * S, dtype=torch.float32, device=dev)
+    lse2 = torch.empty(B * Hq * S, dtype=torch.float32, device=dev)
+    dsinks = part = None
+    if sinks is not None:
+        dsinks = torch.empty(Hq, dtype=torch.float32, device=dev)
+        part = torch.empty(B * Hq * (S // 256), dtype=torch.float32, device=dev)
+    lib = get_lib()
+    with _prof("attn_bwd", 3.0 * 2 * 2 * S * S * Hq * D * 0.5 * B):
+        check(lib.vh_attn64_bwd_pre_bf16(
+            dptr(do), dptr(o), dptr(lse.contiguous()),
+            dptr(sinks) if sinks is not None else None, dptr(delta), dptr(lse2),
+            dptr(dsinks) if dsinks is not None else None,
+            dptr(part) if part is not None else None,
+            B, Hq, S, cur_stream()), "vh_attn64_bwd_pre")
+        dq = torch.empty_like(q)
+        dk = torch.empty_like(k)
+        dv = torch.empty_like(v)
+        check(lib.vh_attn64_bwd2_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(do), dptr(delta), dptr(lse2),
+            dptr(dq), dptr(dk), dptr(dv), B, Hq, Hkv, S, scale,
+            dptr(lo) if lo is not None else None,
+            dptr(hi) if hi is not None else None,
+            cur_stream()), "vh_attn64_bwd2")
     return dq, dk, dv, dsinks
 
 

@@ -5,8 +5,9 @@ Parity target: flash_attention_forward + prepare/restore Ulysses exchange
 seq-sharded/full-heads -> (a2a) -> full-seq/head-sharded -> kernel ->
 (a2a back); GQA KV head repeat when sp > kv heads.
 
-Core kernel (round 2+): the in-repo CDNA4 flash pair (vh_attn_fwd_bf16 /
-vh_attn_bwd2_bf16) including the packed-varlen cu_seqlens path; torch SDPA
+Core kernel (round 2+): the in-repo CDNA4 flash pairs (vh_attn_fwd_bf16 /
+vh_attn_bwd2_bf16 for head_dim 128, vh_attn64_* for head_dim 64) including
+the packed-varlen cu_seqlens path, key windows and sinks; torch SDPA
 (CK/AOTriton) remains as the A/B comparison core. The Ulysses layout
 exchanges are the §8a items and are implemented here.
 """
@@ -30,6 +31,10 @@ from ..kernel_registry import KERNEL_REGISTRY, HardwareRequirement, KernelSpec
 # VEOMNI_ATTN_CORE.
 import os
 _DEFAULT_CORE = os.environ.get("VEOMNI_ATTN_CORE", "hip_flash")
+# head_dim 64 takes the HIP pair by default in every case it covers: with a
+# window, sinks or document bounds the torch core materialises S x S tensors,
+# and for plain single-document causal the pair measured faster forward+
+# backward than SDPA's own flash kernel (profiles/attn_d64_microbench.md).
 
 
 def docs_from_cu_seqlens(cu: torch.Tensor, seq_len: int):
@@ -193,7 +198,9 @@ def eager_window_sink_attention(q, k, v, scaling, lo=None, sinks=None,
 
 class _HipFlashAttention(torch.autograd.Function):
     """In-repo CDNA4 flash kernel pair (vh_attn_fwd_bf16 / vh_attn_bwd2_bf16;
-    csrc/vh_attention.hip). Causal, GQA, D=128, S % 256 == 0, bf16; optional
+    csrc/vh_attention.hip), and its head_dim 64 twin (vh_attn64_*;
+    csrc/vh_attention64.hip), picked by q.shape[-1]. Causal, GQA, D in
+    {128, 64}, S % 256 == 0, bf16; optional
     packed-varlen block-diagonal masking via per-token document bounds
     (the reference's flash-attn cu_seqlens path, attention/flash.py:61-91).
     sinks (fp32 [Hq], differentiable) and shared_bounds (doc_start / doc_end
@@ -211,6 +218,19 @@ class _HipFlashAttention(torch.autograd.Function):
     def forward(ctx, q, k, v, scale, doc_start, doc_end, token_major=False,
                 sinks=None, shared_bounds=False):
         from .. import hip_lib
+        ctx.d64 = q.shape[-1] == 64
+        if ctx.d64:
+            # head_dim 64 (csrc/vh_attention64.hip): one head-major call set
+            # for every case; saved and differentiated like win_sink below
+            assert not token_major, "token_major output needs head_dim 128"
+            assert (doc_start is None) == (doc_end is None)
+            sk = sinks.detach().contiguous() if sinks is not None else None
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            o, lse = hip_lib.attn64_fwd(q, k, v, scale, doc_start, sk)
+            ctx.save_for_backward(q, k, v, o, lse, sk)
+            ctx.scale = scale
+            ctx.docs = (doc_start, doc_end)
+            return o
         ctx.win_sink = sinks is not None or shared_bounds
         if ctx.win_sink:
             assert (doc_start is None) == (doc_end is None)
@@ -239,6 +259,11 @@ class _HipFlashAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         from .. import hip_lib
+        if ctx.d64:
+            q, k, v, o, lse, sk = ctx.saved_tensors
+            dq, dk, dv, dsinks = hip_lib.attn64_bwd(
+                q, k, v, o, lse, do, ctx.scale, *ctx.docs, sk)
+            return dq, dk, dv, None, None, None, None, dsinks, None
         if ctx.win_sink:
             q, k, v, o, lse, sk = ctx.saved_tensors
             dq, dk, dv, dsinks = hip_lib.attn_bwd_win_sink(
@@ -260,8 +285,15 @@ def hip_flash_attention(q, k, v, scale, doc_start=None, doc_end=None,
     documents if there are any; B > 1 is fine without documents.
     sinks: [h] attention-sink logits, differentiable.
     shared_bounds: doc_start / doc_end already are window bounds shared by
-    the batch (what sliding_window builds)."""
+    the batch (what sliding_window builds).
+    D is 128 or 64; token_major needs D = 128."""
     S = q.shape[2]
+    if q.shape[-1] not in (64, 128):
+        raise ValueError(f"hip_flash_attention: head_dim must be 64 or 128, "
+                         f"got {q.shape[-1]}")
+    if q.shape[-1] == 64 and token_major:
+        raise ValueError("hip_flash_attention: token_major output is "
+                         "implemented for head_dim 128 only")
     if doc_start is not None and not shared_bounds:
         assert q.shape[0] == 1, "packed varlen requires B == 1"
     if check_sliding_window(sliding_window) is not None:
@@ -323,10 +355,11 @@ def hip_attention_forward(module, query, key, value, attention_mask,
         doc_start, doc_end = docs_from_cu_seqlens(kwargs["cu_seq_lens_q"],
                                                   q.shape[2])
     core = kwargs.get("core", _DEFAULT_CORE)
-    if core == "hip_flash" and (q.shape[-1] != 128 or q.shape[2] % 256 != 0
+    if core == "hip_flash" and (q.shape[-1] not in (64, 128)
+                                or q.shape[2] % 256 != 0
                                 or q.dtype != torch.bfloat16):
-        # the in-repo pair covers the BASELINE shapes (D=128, S%256, bf16);
-        # toy/unit shapes take the torch core (a dispatch policy, not a
+        # the in-repo pairs cover D in {128, 64}, S % 256, bf16; toy/unit
+        # shapes take the torch core (a dispatch policy, not a
         # missing-extension fallback)
         core = "sdpa"
     if core == "hip_flash":
@@ -337,8 +370,7 @@ def hip_attention_forward(module, query, key, value, attention_mask,
                                   sliding_window=sliding_window)
     elif sliding_window is not None or s_aux is not None:
         # explicit window / document mask plus the sink column. This is the
-        # core that D != 128, S % 256 != 0 and fp32 take, gpt-oss's
-        # head_dim = 64 included.
+        # core that D outside {64, 128}, S % 256 != 0 and fp32 take.
         if scaling is None:
             scaling = q.shape[-1] ** -0.5
         lo, _ = window_bounds(q.shape[2], sliding_window, doc_start, doc_end,

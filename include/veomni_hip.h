@@ -132,6 +132,45 @@ int vh_group_gemm_wgd_bf16(const uint16_t* A, const uint16_t* B, uint16_t* C,
                            const int64_t* cumsum, int G, int64_t M, int64_t N,
                            int64_t total_rows, void* stream);
 
+/* ---- Grouped GEMMs with token rows fed through an index ----------------
+ * The MoE token gather folded into the operand staging: instead of an
+ * expanded [total_rows, K] copy in expert order, the kernel gets the
+ * [n_src, K] source tensor and row_src (int32 [total_rows]); sorted row r
+ * reads source row row_src[r]. Contract: 0 <= row_src[r] < n_src (a loaded
+ * index is clamped into that range, so a bad one cannot fault). Results are
+ * bit-equal to the unindexed kernel on the materialised gather. Only the
+ * 256-square kernels take an index; the predicates below are the one place
+ * that says for which shapes, and callers materialise the rows otherwise. */
+
+/* 1 if vh_group_gemm_nk_bf16 (no accumulate / activation) runs this shape
+ * on nk256s, i.e. vh_group_gemm_nk_idx_bf16 accepts it: K % 64 == 0,
+ * N >= 256, total_rows >= 256*G, G <= 4096. */
+int vh_group_gemm_nk_takes_index(int G, int64_t N, int64_t K,
+                                 int64_t total_rows);
+
+/* vh_group_gemm_nk_bf16 (either trans_b) with A = src[row_src]: A is
+ * [n_src, K], C [total_rows, N]. An error for shapes the predicate rejects. */
+int vh_group_gemm_nk_idx_bf16(const uint16_t* A, const int32_t* row_src,
+                              int64_t n_src, const uint16_t* B, uint16_t* C,
+                              const int64_t* cumsum, int G, int64_t N,
+                              int64_t K, int64_t total_rows, int trans_b,
+                              void* stream);
+
+/* 1 if the direct wgrad kernel serves this shape (M, N >= 512,
+ * total_rows >= 2048); smaller ones go to vh_group_gemm_mn_bf16. */
+int vh_group_gemm_mn_takes_wgd(int64_t M, int64_t N, int64_t total_rows);
+
+/* vh_group_gemm_wgd_bf16 with one operand's rows through row_src:
+ * index_b == 0: A is [n_src, M] and A_g = A[row_src[rows of g]];
+ * index_b != 0: B is [n_src, N] likewise. The other operand is
+ * [total_rows, .] as before. The index entries of k-tile kt+2 are fetched
+ * when tile kt+1 is staged. An error for shapes the predicate rejects. */
+int vh_group_gemm_wgd_idx_bf16(const uint16_t* A, const uint16_t* B,
+                               uint16_t* C, const int64_t* cumsum, int G,
+                               int64_t M, int64_t N, int64_t total_rows,
+                               const int32_t* row_src, int64_t n_src,
+                               int index_b, void* stream);
+
 /* ---- Fused MoE elementwise --------------------------------------------- */
 
 /* Fused epilogue: act = silu(gate) * up * w_row, where gate/up are the two

@@ -18,10 +18,12 @@ OUT = os.path.join(PKG, "libveomni_hip.so")
 # Sources compiled on their own with extra flags and linked in as objects
 # (the other sources keep the one-command build and its code generation).
 # vh_attention64.hip: no packed-fp32 VALU forms (v_pk_mul_f32 and friends) in
-# the softmax stream.
+# the softmax stream. vh_group_gemm8.hip: the same flag for the indexed
+# kernels (the file's ISA has no packed-fp32 instruction either way).
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "vh_attention64.hip": ["-Xclang", "-target-feature", "-Xclang",
-                           "-packed-fp32-ops"],
+    "vh_attention64.hip": _NO_PK_F32,
+    "vh_group_gemm8.hip": _NO_PK_F32,
 }
 
 SOURCES = [

@@ -353,6 +353,14 @@ __global__ __launch_bounds__(THREADS, 2) void k_group_gemm_mn(
 
 }  // namespace
 
+// The one place that decides which shapes run the persistent 256-square
+// nk256s kernels (and so which shapes can take their A rows through an index).
+extern "C" int vh_group_gemm_nk_takes_index(int G, int64_t N, int64_t K,
+                                            int64_t total_rows) {
+  return K % 64 == 0 && N >= 256 && total_rows >= (int64_t)G * 256 &&
+         G <= 4096;
+}
+
 extern "C" int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B,
                                      uint16_t* C, const int64_t* cumsum, int G,
                                      int64_t N, int64_t K, int64_t total_rows,
@@ -366,8 +374,8 @@ extern "C" int vh_group_gemm_nk_bf16(const uint16_t* A, const uint16_t* B,
   //                      stored and read with transposing LDS reads)
   //   !trans_b wide, K % 64 == 32 or G > 4096 -> nk8 (glds A + transposed B ring)
   //   everything else -> the 128x128 2-phase kernel
-  if (!accumulate && activation == 0 && K % 64 == 0 && N >= 256 &&
-      total_rows >= (int64_t)G * 256 && G <= 4096) {
+  if (!accumulate && activation == 0 &&
+      vh_group_gemm_nk_takes_index(G, N, K, total_rows)) {
     // nk256s: device-built tile schedule + XCD-clustered persistent blocks
     // (L2 reuse; no skew-sized null-block grid) — see vh_group_gemm8.hip
     if (trans_b)

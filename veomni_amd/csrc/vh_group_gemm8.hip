@@ -4,6 +4,18 @@
 // straight from the token-major operands). Retired variants are at commits
 // 49b7734 and 2f18dcb; what they measured is in DESIGN.md.
 //
+// Indexed variants (profiles/moe_indexed_operands_ab.md): nk256s<BKN, IDX_A>
+// and wgd256s<IDX_A, IDX_B> read one operand's token rows through
+// row_src (int32 [rows], sorted row -> source row of an [n_src, .] tensor),
+// which replaces the expert-ordered moe_scatter copy of the activations.
+// Only the row address of the glds changes: LDS image, tile walk, MFMA order
+// and epilogue are shared, so the results are bit-equal to the plain kernel
+// on the gathered operand. nk256s loads its four indices per lane once per
+// tile, where the row pointers are hoisted; wgd256s needs four per k-tile
+// and fetches those of tile kt+2 when tile kt+1 is staged. A loaded index is
+// clamped into [0, n_src - 1]. Entry points: vh_group_gemm_nk_idx_bf16,
+// vh_group_gemm_wgd_idx_bf16.
+//
 // nk8: the deep-pipelined variant of vh_group_gemm.hip's same-NK kernel, built on
 // the guide's 256-square 8-phase recipe (cdna_hip_programming.md §5 "The 256²
 // 8-phase template" + T3/T4/T5): counted vmcnt (loads stay in flight across
@@ -25,6 +37,7 @@
 // G > 4096).
 
 #include "vh_common.h"
+#include "../../include/veomni_hip.h"
 
 #include <type_traits>
 
@@ -516,6 +529,25 @@ struct KStage64 {  // [256][64] tile via 4 glds of 8 KiB (512 threads)
     }
   }
 
+  // The same pointers, computed with one swizzled column for the four
+  // instructions: they are 64 rows apart and swz64 reads row bits 0..5 only.
+  // Used by the indexed A operand, where four hoisted per-instruction column
+  // bases cost the registers that kernel does not have.
+  template <typename RowFn>
+  __device__ __forceinline__ void init_onecol(const bf16_t* s, int64_t ld_elems,
+                                              RowFn row_of, int tid) {
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int o = wave * 1024 + lane * 16;
+    const int row0 = o >> 7;
+    const int col = swz64(row0, o & 127) >> 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      src[i] = s + row_of(i * 64 + row0) * ld_elems + col;
+      lds_base[i] = i * 8192 + wave * 1024;
+    }
+  }
+
   __device__ __forceinline__ void stage(bf16_t* tile, int64_t k0) const {
 #pragma unroll
     for (int i = 0; i < 4; ++i) glds16(src[i] + k0, tile + (lds_base[i] >> 1));
@@ -596,6 +628,15 @@ struct TStage64 {  // [64 k][256 out] tile via 4 glds of 8 KiB (512 threads)
     for (int i = 0; i < 4; ++i)
       glds16(src + (int64_t)row_of(k0 + i * 16 + krow) * ld,
              tile + ((i * 8192 + wave * 1024) >> 1));
+  }
+
+  // The same with this lane's four source rows already resolved (rows[i] for
+  // k-row i * 16 + krow): the indexed operands, whose rows come through a
+  // row index fetched one k-tile ahead.
+  __device__ __forceinline__ void stage_rows(bf16_t* tile, const int (&rows)[4]) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      glds16(src + (int64_t)rows[i] * ld, tile + ((i * 8192 + wave * 1024) >> 1));
   }
 
   // Zero the k-rows >= rem that THIS wave staged (call after vmcnt(0), before
@@ -708,11 +749,18 @@ __global__ void k_gg_sched(const int64_t* __restrict__ cumsum, int G,
 // B tile is a "reduction-slow" [64 k][256 n] tile (TStage64 / tr_issue).
 // The k-to-lane map of the fragments is the same in both, so both feed the
 // MFMAs identical operands in identical order.
-template <bool BKN>
+// IDX_A: A is an [n_src, K] tensor and row r of the sorted row space reads
+// its row row_src[r] (the MoE token gather folded into the staging: no
+// expanded copy of the activations). The four index loads per lane happen
+// once per tile, where the row pointers are hoisted; the k-loop is the same.
+// A loaded index is clamped into [0, n_src - 1] (one v_min_u32): the contract
+// is an in-range index, the clamp only keeps a bad one from faulting.
+template <bool BKN, bool IDX_A = false>
 __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
     bf16_t* __restrict__ C, const int64_t* __restrict__ cumsum, int G,
-    int64_t N, int64_t K, int tiles_n, const int* __restrict__ ws) {
+    int64_t N, int64_t K, int tiles_n, const int* __restrict__ ws,
+    const int* __restrict__ row_src, int n_src) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* sm = reinterpret_cast<bf16_t*>(smem);
   auto ta = [&](int buf) { return sm + buf * 32768; };          // 2 x 32 KiB
@@ -746,16 +794,24 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_nk256s(
 
     const int64_t row_start = (gid > 0) ? cumsum[gid - 1] : 0;
     const int64_t m_size = cumsum[gid] - row_start;
-    const bf16_t* Ag = A + row_start * K;
+    const bf16_t* Ag = IDX_A ? A : A + row_start * K;
     const bf16_t* Bg = B + (int64_t)gid * N * K;
     bf16_t* Cg = C + row_start * N;
 
     KStage64 sa, sb;
     TStage64 sbt;
-    sa.init(Ag, K, [&](int r) -> int64_t {
-      int64_t gm = (int64_t)bm * BM8 + r;
-      return gm % m_size;
-    }, tid);
+    if constexpr (IDX_A) {
+      sa.init_onecol(Ag, K, [&](int r) -> int64_t {
+        int64_t gm = (int64_t)bm * BM8 + r;
+        return (int64_t)min((unsigned)row_src[row_start + gm % m_size],
+                            (unsigned)(n_src - 1));
+      }, tid);
+    } else {
+      sa.init(Ag, K, [&](int r) -> int64_t {
+        int64_t gm = (int64_t)bm * BM8 + r;
+        return gm % m_size;
+      }, tid);
+    }
     if constexpr (BKN) {
       sbt.init(Bg, N, [&](int c) -> int64_t {
         return ((int64_t)bn * BN8 + c) % N;
@@ -881,7 +937,8 @@ static constexpr int VH_GG_SCHED_MAX_G = 4096;
 
 static int vh_launch_nk256s(bool b_kn, const uint16_t* A, const uint16_t* B,
                             uint16_t* C, const int64_t* cumsum, int G,
-                            int64_t N, int64_t K, void* stream) {
+                            int64_t N, int64_t K, void* stream,
+                            const int32_t* row_src = nullptr, int n_src = 0) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   VH_CHECK(K % BK64 == 0, "K %% 64 != 0");
   VH_CHECK(N % 16 == 0, "N %% 16 != 0");
@@ -894,11 +951,13 @@ static int vh_launch_nk256s(bool b_kn, const uint16_t* A, const uint16_t* B,
                      vh_gg_sched_ws);
   VH_HIP(hipGetLastError());
   auto kern = b_kn ? k_group_gemm_nk256s<true> : k_group_gemm_nk256s<false>;
+  if (row_src != nullptr)
+    kern = b_kn ? k_group_gemm_nk256s<true, true> : k_group_gemm_nk256s<false, true>;
   hipLaunchKernelGGL(kern, dim3(256), dim3(THREADS8), 131072, s,
                      reinterpret_cast<const bf16_t*>(A),
                      reinterpret_cast<const bf16_t*>(B),
                      reinterpret_cast<bf16_t*>(C), cumsum, G, N, K, tiles_n,
-                     vh_gg_sched_ws);
+                     vh_gg_sched_ws, row_src, n_src);
   VH_HIP(hipGetLastError());
   return 0;
 }
@@ -917,6 +976,24 @@ extern "C" int vh_group_gemm_nk256s_kn_bf16(const uint16_t* A, const uint16_t* B
                                             int64_t total_rows, void* stream) {
   (void)total_rows;
   return vh_launch_nk256s(true, A, B, C, cumsum, G, N, K, stream);
+}
+
+extern "C" int vh_group_gemm_nk_idx_bf16(const uint16_t* A,
+                                         const int32_t* row_src, int64_t n_src,
+                                         const uint16_t* B, uint16_t* C,
+                                         const int64_t* cumsum, int G,
+                                         int64_t N, int64_t K,
+                                         int64_t total_rows, int trans_b,
+                                         void* stream) {
+  VH_CHECK(row_src != nullptr, "row_src is null");
+  VH_CHECK(n_src >= 1 && n_src <= INT32_MAX, "n_src %lld out of range",
+           (long long)n_src);
+  VH_CHECK(vh_group_gemm_nk_takes_index(G, N, K, total_rows),
+           "shape not served by the indexed kernel (G=%d N=%lld K=%lld "
+           "rows=%lld): materialise the rows",
+           G, (long long)N, (long long)K, (long long)total_rows);
+  return vh_launch_nk256s(trans_b == 0, A, B, C, cumsum, G, N, K, stream,
+                          row_src, (int)n_src);
 }
 
 // ============================================================================
@@ -946,10 +1023,14 @@ extern "C" int vh_group_gemm_nk256s_kn_bf16(const uint16_t* A, const uint16_t* B
 
 namespace {
 
+template <bool IDX_A = false, bool IDX_B = false>
 __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wgd256s(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
     bf16_t* __restrict__ C, const int64_t* __restrict__ cumsum, int G,
-    int64_t M, int64_t N, int tiles_m, int tiles_n) {
+    int64_t M, int64_t N, int tiles_m, int tiles_n,
+    const int* __restrict__ row_src, int n_src) {
+  static_assert(!(IDX_A && IDX_B), "one indexed operand at most");
+  constexpr bool IDX = IDX_A || IDX_B;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* sm = reinterpret_cast<bf16_t*>(smem);
   auto ta = [&](int buf) { return sm + buf * 32768; };
@@ -985,10 +1066,10 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wgd256s(
 
     if (cnt > 0) {
       TStage64 sa, sb;
-      sa.init(A + row_start * M, M, [&](int c) -> int64_t {
+      sa.init(IDX_A ? A : A + row_start * M, M, [&](int c) -> int64_t {
         return ((int64_t)bm * BM8 + c) % M;
       }, tid);
-      sb.init(B + row_start * N, N, [&](int c) -> int64_t {
+      sb.init(IDX_B ? B : B + row_start * N, N, [&](int c) -> int64_t {
         return ((int64_t)bn * BN8 + c) % N;
       }, tid);
       // clamp to the group's last row: in bounds for every k of every tile
@@ -996,10 +1077,33 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wgd256s(
 
       const int nk = (cnt + BK64 - 1) / BK64;
       const int rem = cnt - (nk - 1) * BK64;  // valid k-rows of the last tile
+      // Indexed operand: this lane's four raw row_src entries for the NEXT
+      // tile to stage. fetch(kt) is issued right after tile kt - 1 is staged,
+      // so the loads fly under a whole k-tile of MFMAs and the VMCNT(0) at the
+      // loop end covers them: no dependent load in front of a glds. The clamp
+      // into [0, n_src - 1] is applied where the value is used.
+      int nxt[4];
+      auto fetch = [&](int kt) {
+        if constexpr (IDX) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            nxt[i] = row_src[row_start + row_of(kt * BK64 + i * 16 + sa.krow)];
+        }
+      };
+      auto stage_idx = [&](const TStage64& st, bf16_t* tile) {
+        int rows[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          rows[i] = (int)min((unsigned)nxt[i], (unsigned)(n_src - 1));
+        st.stage_rows(tile, rows);
+      };
       // stage k-tile kt; the group's last tile gets its tail rows zeroed
       auto stage = [&](int buf, int kt) {
-        sa.stage(ta(buf), kt * BK64, row_of);
-        sb.stage(tb(buf), kt * BK64, row_of);
+        if constexpr (IDX_A) stage_idx(sa, ta(buf));
+        else sa.stage(ta(buf), kt * BK64, row_of);
+        if constexpr (IDX_B) stage_idx(sb, tb(buf));
+        else sb.stage(tb(buf), kt * BK64, row_of);
+        fetch(kt + 1);
       };
       auto zero_tail = [&](int buf) {
         VMCNT(0);
@@ -1013,6 +1117,7 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wgd256s(
 #pragma unroll
       for (int j = 0; j < 4; ++j) btr_off[j] = tr_lane_off(wc * 64 + j * 16, lane);
 
+      fetch(0);
       stage(0, 0);
       if (nk == 1 && rem < BK64) zero_tail(0);
       VMCNT(0);
@@ -1083,21 +1188,54 @@ __global__ __launch_bounds__(THREADS8, 2) void k_group_gemm_wgd256s(
 
 }  // namespace
 
-extern "C" int vh_group_gemm_wgd_bf16(const uint16_t* A, const uint16_t* B,
-                                      uint16_t* C, const int64_t* cumsum, int G,
-                                      int64_t M, int64_t N, int64_t total_rows,
-                                      void* stream) {
+// idx_operand: 0 none, 1 A rows through row_src, 2 B rows through row_src
+static int vh_launch_wgd256s(const uint16_t* A, const uint16_t* B, uint16_t* C,
+                             const int64_t* cumsum, int G, int64_t M, int64_t N,
+                             const int32_t* row_src, int n_src, int idx_operand,
+                             void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  (void)total_rows;
   VH_CHECK(M % 16 == 0 && N % 16 == 0, "M/N %% 16 != 0");
   VH_CHECK(G >= 1, "G < 1");
   int tiles_m = (int)((M + BM8 - 1) / BM8);
   int tiles_n = (int)((N + BN8 - 1) / BN8);
-  hipLaunchKernelGGL(k_group_gemm_wgd256s, dim3(256), dim3(THREADS8), 131072, s,
+  auto kern = k_group_gemm_wgd256s<false, false>;
+  if (idx_operand == 1) kern = k_group_gemm_wgd256s<true, false>;
+  if (idx_operand == 2) kern = k_group_gemm_wgd256s<false, true>;
+  hipLaunchKernelGGL(kern, dim3(256), dim3(THREADS8), 131072, s,
                      reinterpret_cast<const bf16_t*>(A),
                      reinterpret_cast<const bf16_t*>(B),
                      reinterpret_cast<bf16_t*>(C), cumsum, G, M, N, tiles_m,
-                     tiles_n);
+                     tiles_n, row_src, n_src);
   VH_HIP(hipGetLastError());
   return 0;
+}
+
+extern "C" int vh_group_gemm_mn_takes_wgd(int64_t M, int64_t N,
+                                          int64_t total_rows) {
+  return M >= 512 && N >= 512 && total_rows >= 2048;
+}
+
+extern "C" int vh_group_gemm_wgd_bf16(const uint16_t* A, const uint16_t* B,
+                                      uint16_t* C, const int64_t* cumsum, int G,
+                                      int64_t M, int64_t N, int64_t total_rows,
+                                      void* stream) {
+  (void)total_rows;
+  return vh_launch_wgd256s(A, B, C, cumsum, G, M, N, nullptr, 0, 0, stream);
+}
+
+extern "C" int vh_group_gemm_wgd_idx_bf16(const uint16_t* A, const uint16_t* B,
+                                          uint16_t* C, const int64_t* cumsum,
+                                          int G, int64_t M, int64_t N,
+                                          int64_t total_rows,
+                                          const int32_t* row_src, int64_t n_src,
+                                          int index_b, void* stream) {
+  VH_CHECK(row_src != nullptr, "row_src is null");
+  VH_CHECK(n_src >= 1 && n_src <= INT32_MAX, "n_src %lld out of range",
+           (long long)n_src);
+  VH_CHECK(vh_group_gemm_mn_takes_wgd(M, N, total_rows),
+           "shape not served by the indexed kernel (M=%lld N=%lld rows=%lld): "
+           "materialise the rows",
+           (long long)M, (long long)N, (long long)total_rows);
+  return vh_launch_wgd256s(A, B, C, cumsum, G, M, N, row_src, (int)n_src,
+                           index_b ? 2 : 1, stream);
 }

@@ -58,6 +58,12 @@ def get_lib() -> ctypes.CDLL:
     _sig(lib, "vh_wtranspose_bf16", c_p, c_p, c_int, c_i64, c_i64, c_p)
     _sig(lib, "vh_group_gemm_wgd_bf16", c_p, c_p, c_p, c_p, c_int, c_i64,
          c_i64, c_i64, c_p)
+    _sig(lib, "vh_group_gemm_nk_takes_index", c_int, c_i64, c_i64, c_i64)
+    _sig(lib, "vh_group_gemm_nk_idx_bf16", c_p, c_p, c_i64, c_p, c_p, c_p, c_int,
+         c_i64, c_i64, c_i64, c_int, c_p)
+    _sig(lib, "vh_group_gemm_mn_takes_wgd", c_i64, c_i64, c_i64)
+    _sig(lib, "vh_group_gemm_wgd_idx_bf16", c_p, c_p, c_p, c_p, c_int, c_i64,
+         c_i64, c_i64, c_p, c_i64, c_int, c_p)
     _sig(lib, "vh_moe_silu_mul_weighted_bf16", c_p, c_p, c_p, c_i64, c_i64, c_int, c_p)
     _sig(lib, "vh_moe_silu_mul_weighted_bwd_bf16", c_p, c_p, c_p, c_p, c_p,
          c_i64, c_i64, c_int, c_p)
@@ -224,15 +230,41 @@ def moe_gather(x: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _row_index(rows: torch.Tensor) -> torch.Tensor:
+    assert rows.dtype == torch.int32 and rows.dim() == 1
+    return rows.contiguous()
+
+
 def group_gemm_nk(a: torch.Tensor, b: torch.Tensor, cumsum: torch.Tensor,
                   trans_b: bool, c: torch.Tensor | None = None,
-                  activation: int = 0) -> torch.Tensor:
-    """C_g = A_g @ (B_g^T if trans_b else B_g); rows partitioned by cumsum."""
+                  activation: int = 0,
+                  a_rows: torch.Tensor | None = None) -> torch.Tensor:
+    """C_g = A_g @ (B_g^T if trans_b else B_g); rows partitioned by cumsum.
+
+    a_rows (int32 [rows], entries in [0, a.shape[0])): the A operand is
+    a[a_rows], read through the index by the 256-square kernels (no gathered
+    copy). Shapes those kernels do not take (the library decides:
+    vh_group_gemm_nk_takes_index) get the rows materialised and run as
+    before."""
     assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16
     G = b.shape[0]
     N = b.shape[1] if trans_b else b.shape[2]
     K = b.shape[2] if trans_b else b.shape[1]
     assert a.shape[1] == K, (a.shape, b.shape, trans_b)
+    if a_rows is not None:
+        a_rows = _row_index(a_rows)
+        rows = a_rows.numel()
+        if c is None and activation == 0 and get_lib().vh_group_gemm_nk_takes_index(
+                G, N, K, rows):
+            c = torch.empty(rows, N, dtype=a.dtype, device=a.device)
+            cs = cumsum.to(torch.int64).contiguous()
+            with _prof("group_gemm_nk", 2.0 * rows * N * K):
+                check(get_lib().vh_group_gemm_nk_idx_bf16(
+                    dptr(a.contiguous()), dptr(a_rows), a.shape[0],
+                    dptr(b.contiguous()), dptr(c), dptr(cs), G, N, K, rows,
+                    int(trans_b), cur_stream()), "vh_group_gemm_nk_idx")
+            return c
+        a = a.index_select(0, a_rows)
     if K % 64 != 0:
         # zero-pad the reduction dim to the kernel's BK multiple (only test
         # shapes hit this; every production K — H, I, 2I — is a 64-multiple)
@@ -254,18 +286,43 @@ def group_gemm_nk(a: torch.Tensor, b: torch.Tensor, cumsum: torch.Tensor,
 
 
 def group_gemm_mn(a: torch.Tensor, b: torch.Tensor, cumsum: torch.Tensor,
-                  G: int) -> torch.Tensor:
+                  G: int, a_rows: torch.Tensor | None = None,
+                  b_rows: torch.Tensor | None = None) -> torch.Tensor:
     """C[g] = A_g^T @ B_g; A [rows, M], B [rows, N] -> C [G, M, N].
 
     Large shapes take the direct wgrad kernel: both operands are read
     token-major as they are (no transposed/padded copies, no temporaries);
-    the kernel stages [64 k][256 out] tiles and transposes in the LDS read."""
+    the kernel stages [64 k][256 out] tiles and transposes in the LDS read.
+
+    a_rows / b_rows (int32 [rows], at most one of them): that operand is
+    a[a_rows] / b[b_rows], read through the index by the direct kernel; for
+    the shapes it does not take (vh_group_gemm_mn_takes_wgd) the rows are
+    materialised first."""
     assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16
-    rows = a.shape[0]
+    assert a_rows is None or b_rows is None
+    idx = a_rows if a_rows is not None else b_rows
+    if idx is not None:
+        idx = _row_index(idx)
+    rows = idx.numel() if idx is not None else a.shape[0]
     M, N = a.shape[1], b.shape[1]
+    direct = bool(get_lib().vh_group_gemm_mn_takes_wgd(M, N, rows))
+    if idx is not None and not direct:
+        if a_rows is not None:
+            a = a.index_select(0, idx)
+        else:
+            b = b.index_select(0, idx)
+        idx = None
     c = torch.empty(G, M, N, dtype=a.dtype, device=a.device)
     cs = cumsum.to(torch.int64).contiguous()
-    if M >= 512 and N >= 512 and rows >= 2048:
+    if idx is not None:
+        n_src = a.shape[0] if a_rows is not None else b.shape[0]
+        with _prof("group_gemm_mn", 2.0 * rows * M * N):
+            check(get_lib().vh_group_gemm_wgd_idx_bf16(
+                dptr(a.contiguous()), dptr(b.contiguous()), dptr(c), dptr(cs), G,
+                M, N, rows, dptr(idx), n_src, int(b_rows is not None),
+                cur_stream()), "vh_group_gemm_wgd_idx")
+        return c
+    if direct:
         with _prof("group_gemm_mn", 2.0 * rows * M * N):
             check(get_lib().vh_group_gemm_wgd_bf16(
                 dptr(a.contiguous()), dptr(b.contiguous()), dptr(c), dptr(cs), G,

@@ -11,8 +11,11 @@ Parity targets:
   - scatter-index helper kept plain torch ON PURPOSE, like the reference
     (_scatter.py:30-33: "plain-torch helper on purpose").
 
-Device work: vh_expert_histogram / vh_moe_scatter / vh_group_gemm_nk /
-vh_moe_silu_mul_weighted / vh_group_gemm_mn / vh_moe_gather (C ABI).
+Device work: vh_expert_histogram / vh_group_gemm_nk / vh_moe_silu_mul_weighted
+/ vh_group_gemm_mn / vh_moe_gather (C ABI). The non-EP classes make no
+expert-ordered copy of the activations: the grouped GEMMs read token rows
+through row_src (compute_expert_row_src; vh_group_gemm_nk_idx /
+vh_group_gemm_wgd_idx), and vh_moe_scatter is left for the gpt-oss dy_rows.
 
 Clamped SwiGLU (`swiglu_limit`; ref group_gemm.py:24-42, :357-363, :477-480):
 every expert path takes an optional limit and hands it to the epilogue pair,
@@ -54,6 +57,14 @@ def compute_expert_scatter_index(expert_index: torch.Tensor):
     return sorted_order, inv.to(torch.int32).view(expert_index.shape)
 
 
+def compute_expert_row_src(sorted_order: torch.Tensor, topk: int) -> torch.Tensor:
+    """int32 [T*topk]: row_src[r] = the token whose copy lies at sorted row r
+    (scatter_index's inverse, folded to tokens), from the argsort
+    compute_expert_scatter_index returns. The grouped GEMMs read the token
+    rows through it instead of through an expert-ordered copy."""
+    return (sorted_order // topk).to(torch.int32)
+
+
 class HipFusedMoeFunction(torch.autograd.Function):
     """Non-EP merged-fc1 fused MoE (parity: MergedFc1TritonFusedMoeExpertFunction)."""
 
@@ -62,11 +73,14 @@ class HipFusedMoeFunction(torch.autograd.Function):
                 fc1_1_2_weight, fc2_weight, swiglu_limit=None):
         T, H = hidden_states.shape
         splits = hip_lib.expert_histogram(expert_index, num_experts)
-        _, scatter_index = compute_expert_scatter_index(expert_index)
-        scatter_output = hip_lib.moe_scatter(hidden_states, scatter_index)
+        sorted_order, scatter_index = compute_expert_scatter_index(expert_index)
+        # token rows reach the GEMMs through row_src: no expert-ordered copy
+        row_src = compute_expert_row_src(sorted_order, sorted_order.numel() // T)
+        hidden_states = hidden_states.contiguous()
         cumsum_t = torch.cumsum(splits, dim=0)
 
-        fc1 = hip_lib.group_gemm_nk(scatter_output, fc1_1_2_weight, cumsum_t, trans_b=True)
+        fc1 = hip_lib.group_gemm_nk(hidden_states, fc1_1_2_weight, cumsum_t,
+                                    trans_b=True, a_rows=row_src)
 
         w = gate_weights.reshape(-1)
         scattered_w = torch.empty_like(w)
@@ -79,25 +93,28 @@ class HipFusedMoeFunction(torch.autograd.Function):
         ctx.num_experts = num_experts
         ctx.swiglu_limit = swiglu_limit
         ctx.save_for_backward(gate_weights, fc1_1_2_weight, fc2_weight,
-                              scatter_index, scatter_output, cumsum_t, fc1,
-                              scattered_w, weighted)
+                              scatter_index, hidden_states, row_src, cumsum_t,
+                              fc1, scattered_w, weighted)
         return out
 
     @staticmethod
     def backward(ctx, grad_output):
         (gate_weights, fc1_1_2_weight, fc2_weight, scatter_index,
-         scatter_output, cumsum_t, fc1, scattered_w, weighted) = ctx.saved_tensors
+         hidden_states, row_src, cumsum_t, fc1, scattered_w,
+         weighted) = ctx.saved_tensors
         G = fc2_weight.shape[0]
         grad_output = grad_output.view(-1, grad_output.shape[-1]).contiguous()
 
-        grad_fc2_out = hip_lib.moe_scatter(grad_output, scatter_index)
         # dgrad through fc2 straight from the stored [G, H, I] weights: the
         # !trans_b nk256s kernel stages W[g] as it lies and transposes in the
-        # LDS read (no transposed copy; profiles/gg_direct_operands_ab.md)
+        # LDS read (no transposed copy; profiles/gg_direct_operands_ab.md).
+        # grad_output's rows come through row_src, here and in the wgrad
+        # (profiles/moe_indexed_operands_ab.md)
         d_weighted = hip_lib.group_gemm_nk(
-            grad_fc2_out, fc2_weight, cumsum_t, trans_b=False)
+            grad_output, fc2_weight, cumsum_t, trans_b=False, a_rows=row_src)
         # wgrad fc2: [G, H, I]
-        d_fc2_w = hip_lib.group_gemm_mn(grad_fc2_out, weighted, cumsum_t, G)
+        d_fc2_w = hip_lib.group_gemm_mn(grad_output, weighted, cumsum_t, G,
+                                        a_rows=row_src)
 
         # fused epilogue backward (silu — and, with a limit, clamp + mask —
         # recomputed from the saved raw pre-activation)
@@ -109,7 +126,8 @@ class HipFusedMoeFunction(torch.autograd.Function):
         # dgrad + wgrad through merged fc1 (stored weights, as above)
         d_scatter = hip_lib.group_gemm_nk(
             d_fc1, fc1_1_2_weight, cumsum_t, trans_b=False)
-        d_fc1_w = hip_lib.group_gemm_mn(d_fc1, scatter_output, cumsum_t, G)
+        d_fc1_w = hip_lib.group_gemm_mn(d_fc1, hidden_states, cumsum_t, G,
+                                        b_rows=row_src)
 
         grad_hidden = hip_lib.moe_gather(d_scatter, scatter_index)
         return None, grad_gate, None, grad_hidden, d_fc1_w, d_fc2_w, None
@@ -275,11 +293,14 @@ class HipGptOssFusedMoeFunction(torch.autograd.Function):
                 gate_up_proj, gate_up_proj_bias, down_proj, down_proj_bias,
                 alpha, limit):
         splits = hip_lib.expert_histogram(expert_index, num_experts)
-        _, scatter_index = compute_expert_scatter_index(expert_index)
-        x_s = hip_lib.moe_scatter(hidden_states, scatter_index)
+        sorted_order, scatter_index = compute_expert_scatter_index(expert_index)
+        row_src = compute_expert_row_src(
+            sorted_order, sorted_order.numel() // hidden_states.shape[0])
+        hidden_states = hidden_states.contiguous()
         cumsum_t = torch.cumsum(splits, dim=0)
 
-        fc1 = hip_lib.group_gemm_nk(x_s, gate_up_proj, cumsum_t, trans_b=False)
+        fc1 = hip_lib.group_gemm_nk(hidden_states, gate_up_proj, cumsum_t,
+                                    trans_b=False, a_rows=row_src)
         act = hip_lib.gptoss_glu(fc1, gate_up_proj_bias, cumsum_t, alpha, limit)
         fc2 = hip_lib.group_gemm_nk(act, down_proj, cumsum_t, trans_b=False)
 
@@ -292,14 +313,15 @@ class HipGptOssFusedMoeFunction(torch.autograd.Function):
         ctx.alpha, ctx.limit = alpha, limit
         ctx.save_for_backward(gate_weights, gate_up_proj, gate_up_proj_bias,
                               down_proj, down_proj_bias, scatter_index,
-                              cumsum_t, x_s, fc1, act, fc2, scattered_w)
+                              cumsum_t, hidden_states, row_src, fc1, act, fc2,
+                              scattered_w)
         return out
 
     @staticmethod
     def backward(ctx, grad_output):
         (gate_weights, gate_up_proj, gate_up_proj_bias, down_proj,
-         down_proj_bias, scatter_index, cumsum_t, x_s, fc1, act, fc2,
-         scattered_w) = ctx.saved_tensors
+         down_proj_bias, scatter_index, cumsum_t, hidden_states, row_src,
+         fc1, act, fc2, scattered_w) = ctx.saved_tensors
         G = down_proj.shape[0]
         grad_output = grad_output.view(-1, grad_output.shape[-1]).contiguous()
 
@@ -317,7 +339,8 @@ class HipGptOssFusedMoeFunction(torch.autograd.Function):
                                        ctx.alpha, ctx.limit)
         d_gate_up_bias = _bias_grad(d_fc1, cumsum_t, gate_up_proj_bias)
         d_x_s = hip_lib.group_gemm_nk(d_fc1, gate_up_proj, cumsum_t, trans_b=True)
-        d_gate_up = hip_lib.group_gemm_mn(x_s, d_fc1, cumsum_t, G)       # [G, H, 2I]
+        d_gate_up = hip_lib.group_gemm_mn(hidden_states, d_fc1, cumsum_t, G,
+                                          a_rows=row_src)                # [G, H, 2I]
 
         grad_hidden = hip_lib.moe_gather(d_x_s, scatter_index)
         return (None, grad_gate, None, grad_hidden, d_gate_up, d_gate_up_bias,

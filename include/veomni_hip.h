@@ -473,6 +473,41 @@ int vh_attn64_bwd2_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
                         float scale, const int32_t* lo, const int32_t* hi,
                         void* stream);
 
+/* Head dim 80 (csrc/vh_attention80.hip): NON-causal block-diagonal flash
+ * attention for the vision tower, bf16, Hq == Hkv == H, no batch dimension.
+ * Token-major operands: Q, K, V, dO are [S, H, 80] with the head stride
+ * fixed at 80 and one row stride each (q_rs, k_rs, v_rs, do_rs: elements,
+ * multiples of 8, >= H*80; bases 16 B aligned), so a slice of a
+ * [S, 3, H, 80] qkv projection is read in place (row stride 3*H*80).
+ * O, dQ, dK, dV are written [S, H, 80] contiguous; LSE, delta, lse2 are
+ * [H, S] fp32 (lse2 = LSE*log2e).
+ *   seg_lo, seg_hi  int32 [S], both or neither: row i sees key j iff
+ *           seg_lo[i] <= j < seg_hi[i]. Both monotone non-decreasing with
+ *           seg_lo[i] <= i < seg_hi[i] <= S, and block-diagonal: the rows
+ *           that see key j are [seg_lo[j], seg_hi[j]) (the kernels skip
+ *           whole tiles from them). NULL, NULL is one segment [0, S).
+ * Any S >= 1: tail loads are clamped to row S-1 and masked, stores are
+ * predicated. bwd2 writes dQ, dK, dV once each, without atomics; all results
+ * are bit-identical from run to run.
+ * fwd and bwd2: scale > 0. All three: 1 <= H <= 65535, the stride rules. */
+int vh_attn80_fwd_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
+                       uint16_t* O, float* LSE, int H, int64_t S, int64_t q_rs,
+                       int64_t k_rs, int64_t v_rs, float scale,
+                       const int32_t* seg_lo, const int32_t* seg_hi,
+                       void* stream);
+
+int vh_attn80_bwd_pre_bf16(const uint16_t* dO, const uint16_t* O,
+                           const float* LSE, float* delta, float* lse2, int H,
+                           int64_t S, int64_t do_rs, void* stream);
+
+int vh_attn80_bwd2_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
+                        const uint16_t* dO, const float* delta,
+                        const float* lse2, uint16_t* dQ, uint16_t* dK,
+                        uint16_t* dV, int H, int64_t S, int64_t q_rs,
+                        int64_t k_rs, int64_t v_rs, int64_t do_rs, float scale,
+                        const int32_t* seg_lo, const int32_t* seg_hi,
+                        void* stream);
+
 /* ---- Fused optimizer ----------------------------------------------------- */
 
 /* One-sweep AdamW over a device pointer table (torch semantics: decoupled

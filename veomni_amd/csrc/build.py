@@ -23,6 +23,7 @@ OUT = os.path.join(PKG, "libveomni_hip.so")
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "vh_attention64.hip": _NO_PK_F32,
+    "vh_attention80.hip": _NO_PK_F32,   # as vh_attention64.hip
     "vh_group_gemm8.hip": _NO_PK_F32,
 }
 
@@ -36,6 +37,7 @@ SOURCES = [
     "vh_norms.hip",
     "vh_attention.hip",
     "vh_attention64.hip",
+    "vh_attention80.hip",
     "vh_ce.hip",
     "vh_logprob.hip",
     "vh_adamw.hip",

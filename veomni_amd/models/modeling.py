@@ -39,6 +39,7 @@ veomni_gpt_oss_moe_experts_forward = OpSlot("moe_experts", "gpt_oss")
 veomni_causal_lm_loss = OpSlot("cross_entropy_loss", "causal")
 veomni_load_balancing_loss = OpSlot("load_balancing_loss", "standard")
 veomni_attention = OpSlot("attention", "sdpa_with_sp")
+veomni_vision_attention = OpSlot("attention", "vision_varlen")
 
 
 @dataclass
@@ -962,3 +963,7 @@ def bind_ops(impl: str | dict = "eager") -> None:
     # both expert variants follow the one "moe_experts" entry
     veomni_gpt_oss_moe_experts_forward.bind(
         impl if isinstance(impl, str) else impl.get("moe_experts", "eager"))
+    # the vision tower's attention variant follows the "attention" entry; the
+    # hip_flash name of the text slot means the same HIP path here
+    name = impl if isinstance(impl, str) else impl.get("attention", "eager")
+    veomni_vision_attention.bind("hip" if name == "hip_flash" else name)

@@ -17,11 +17,11 @@ generated/patched_modeling_qwen2_5_vl_gpu.py):
     RotaryEmbedding in modeling.py).
 
 MI355X design notes:
-  - the vision tower's windowed attention runs as ONE SDPA call per block
-    over a block-diagonal mask built from the (collator-precomputable)
-    cu_seqlens — vision head_dim (80) is off the hand-written D=128 flash
-    pair's path; the language model runs the standard HIP op stack
-    (hip_flash attention incl. varlen, HIP rms/rope/swiglu/CE).
+  - the vision tower's attention (non-causal, block-diagonal over the
+    collator-precomputable cu_seqlens, head_dim 80) runs on its own HIP
+    flash pair through the attention/vision_varlen OpSlot; the language
+    model runs the standard HIP op stack (hip_flash attention incl. varlen,
+    HIP rms/rope/swiglu/CE).
   - under Ulysses SP the vision tower is REPLICATED (every rank computes
     the full image set; deviation from the reference's ViT SP-slicing —
     simpler, correct, and the tower is a small fraction of step FLOPs);
@@ -42,7 +42,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..distributed.parallel_state import get_parallel_state
-from .modeling import (ForCausalLM, ModelConfig, RMSNorm, rotate_half)
+from ..ops.kernels.attention import eager_vision_attention
+from .modeling import (ForCausalLM, ModelConfig, RMSNorm, rotate_half,
+                       veomni_vision_attention)
 
 
 @dataclass
@@ -115,12 +117,14 @@ def _apply_vision_rope(q, k, cos, sin):
 class VisionAttention(nn.Module):
     """NON-causal varlen attention over [S, hidden] (ref :446-535):
     block-diagonal segments (full-attention blocks use the per-image
-    cu_seqlens, window blocks the window cu_seqlens), executed as MASKLESS
-    batched SDPA over runs of equal-length segments — numerically identical
-    to the bool-masked single call, but it keeps torch on the flash/
-    mem-efficient backend (a bool attn_mask forces the math path, which
-    materializes [h, S, S] scores: 5+ GiB and an OOM at the seq-8192 mbs-4
-    VLM bench shape)."""
+    cu_seqlens, window blocks the window cu_seqlens). The core runs through
+    the attention/vision_varlen OpSlot on [S, heads, D] q, k (after the rope)
+    and the v view of the qkv projection: bound "hip" that is the head_dim 80
+    HIP flash pair (csrc/vh_attention80.hip); bound "eager", unbound, or with
+    core = "sdpa" (the A/B switch) it is eager_vision_attention, the MASKLESS
+    batched SDPA over runs of equal-length segments."""
+
+    core = "slot"        # "slot" | "sdpa"
 
     def __init__(self, cfg: VisionConfig):
         super().__init__()
@@ -135,22 +139,10 @@ class VisionAttention(nn.Module):
         q, k, v = (self.qkv(x).reshape(S, 3, self.num_heads, -1)
                    .permute(1, 0, 2, 3).unbind(0))
         q, k = _apply_vision_rope(q, k, cos, sin)
-        out = torch.empty_like(v)            # [S, h, D]
-        i = 0
-        n_seg = len(cu) - 1
-        while i < n_seg:
-            j = i
-            L = cu[i + 1] - cu[i]
-            while j < n_seg and cu[j + 1] - cu[j] == L:
-                j += 1
-            s0, s1, n = cu[i], cu[j], j - i
-            qs = q[s0:s1].reshape(n, L, self.num_heads, -1).transpose(1, 2)
-            ks = k[s0:s1].reshape(n, L, self.num_heads, -1).transpose(1, 2)
-            vs = v[s0:s1].reshape(n, L, self.num_heads, -1).transpose(1, 2)
-            o = F.scaled_dot_product_attention(qs, ks, vs, scale=self.scaling,
-                                               is_causal=False)
-            out[s0:s1] = o.transpose(1, 2).reshape(n * L, self.num_heads, -1)
-            i = j
+        if self.core == "slot" and veomni_vision_attention.use_non_eager_impl:
+            out = veomni_vision_attention(q, k, v, cu, self.scaling)
+        else:
+            out = eager_vision_attention(q, k, v, cu, self.scaling)
         return self.proj(out.reshape(S, -1))
 
 

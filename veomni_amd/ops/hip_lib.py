@@ -128,6 +128,12 @@ def get_lib() -> ctypes.CDLL:
          c_int, c_int, c_i64, c_p)
     _sig(lib, "vh_attn64_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
+    _sig(lib, "vh_attn80_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_i64,
+         c_i64, c_i64, c_f32, c_p, c_p, c_p)
+    _sig(lib, "vh_attn80_bwd_pre_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_i64,
+         c_i64, c_p)
+    _sig(lib, "vh_attn80_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_fwd", c_p, c_int, c_p, c_i64, c_int, c_int, c_p, c_int, c_p)
     _sig(lib, "vh_lbl_finish", c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p)
     _sig(lib, "vh_lbl_bwd", c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_p)
@@ -1039,6 +1045,80 @@ def attn64_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             dptr(hi) if hi is not None else None,
             cur_stream()), "vh_attn64_bwd2")
     return dq, dk, dv, dsinks
+
+
+def _check_attn80(q, k, v, seg_lo, seg_hi):
+    S, H, D = q.shape
+    assert D == 80 and S >= 1, (S, D)
+    assert k.shape == q.shape and v.shape == q.shape, (q.shape, k.shape, v.shape)
+    for t in (q, k, v):
+        assert t.dtype == torch.bfloat16 and t.is_cuda and t.device == q.device \
+            and t.stride(2) == 1 and t.stride(1) == D and t.stride(0) % 8 == 0 \
+            and t.stride(0) >= H * D and t.data_ptr() % 16 == 0, \
+            "q/k/v: bf16 [S,H,80] on one GPU, head stride 80, row stride % 8"
+    assert (seg_lo is None) == (seg_hi is None)
+    for t in (seg_lo, seg_hi):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (S,)
+                             and t.is_contiguous() and t.device == q.device), \
+            "segments: int32 [S], contiguous, on the inputs' device"
+
+
+def attn80_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+               seg_lo: torch.Tensor | None = None,
+               seg_hi: torch.Tensor | None = None):
+    """Non-causal block-diagonal flash attention forward at head_dim 80
+    (vh_attn80_fwd_bf16): q, k, v [S,H,80] bf16 with head stride 80 and any row
+    stride that is a multiple of 8 (views of a [S,3,H,80] projection are read
+    in place). seg_lo / seg_hi: int32 [S], row i sees keys [seg_lo[i],
+    seg_hi[i]); None, None is one segment. Returns (o [S,H,80] contiguous,
+    lse [H,S] fp32)."""
+    _check_attn80(q, k, v, seg_lo, seg_hi)
+    S, H, D = q.shape
+    o = torch.empty(S, H, D, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(H, S, dtype=torch.float32, device=q.device)
+    with _prof("attn80_fwd"):
+        check(get_lib().vh_attn80_fwd_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(o), dptr(lse), H, S, q.stride(0),
+            k.stride(0), v.stride(0), scale,
+            dptr(seg_lo) if seg_lo is not None else None,
+            dptr(seg_hi) if seg_hi is not None else None,
+            cur_stream()), "vh_attn80_fwd")
+    return o, lse
+
+
+def attn80_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+               o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
+               scale: float, seg_lo: torch.Tensor | None = None,
+               seg_hi: torch.Tensor | None = None):
+    """Backward for attn80_fwd: (dq, dk, dv), each [S,H,80] contiguous and
+    written once (no atomics: the same bits from run to run)."""
+    _check_attn80(q, k, v, seg_lo, seg_hi)
+    S, H, D = q.shape
+    assert o.shape == q.shape and o.is_contiguous() and o.dtype == q.dtype
+    assert do.shape == q.shape and do.dtype == q.dtype, (do.shape, do.dtype)
+    assert lse.shape == (H, S) and lse.dtype == torch.float32 and lse.is_contiguous()
+    if not (do.stride(2) == 1 and do.stride(1) == D and do.stride(0) % 8 == 0
+            and do.stride(0) >= H * D and do.data_ptr() % 16 == 0):
+        do = do.contiguous()
+    dev = q.device
+    delta = torch.empty(H * S, dtype=torch.float32, device=dev)
+    lse2 = torch.empty(H * S, dtype=torch.float32, device=dev)
+    dq = torch.empty(S, H, D, dtype=torch.bfloat16, device=dev)
+    dk = torch.empty_like(dq)
+    dv = torch.empty_like(dq)
+    lib = get_lib()
+    with _prof("attn80_bwd"):
+        check(lib.vh_attn80_bwd_pre_bf16(
+            dptr(do), dptr(o), dptr(lse), dptr(delta), dptr(lse2), H, S,
+            do.stride(0), cur_stream()), "vh_attn80_bwd_pre")
+        check(lib.vh_attn80_bwd2_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(do), dptr(delta), dptr(lse2),
+            dptr(dq), dptr(dk), dptr(dv), H, S, q.stride(0), k.stride(0),
+            v.stride(0), do.stride(0), scale,
+            dptr(seg_lo) if seg_lo is not None else None,
+            dptr(seg_hi) if seg_hi is not None else None,
+            cur_stream()), "vh_attn80_bwd2")
+    return dq, dk, dv
 
 
 # ---------------------------------------------------- load-balancing loss

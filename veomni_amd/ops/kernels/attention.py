@@ -408,6 +408,123 @@ def hip_attention_forward(module, query, key, value, attention_mask,
     return out, None
 
 
+
+# ---- vision tower: non-causal block-diagonal attention (attention/vision_varlen)
+# (id(cu), S, device) -> (cu, seg_lo, seg_hi). The tower hands the same two
+# host lists (image and window cu_seqlens) to all of its blocks and to their
+# recompute, so each pair of bounds is built once per forward; the entry holds
+# on to the list, which keeps its id from being reused.
+_SEGMENTS_CACHE: dict = {}
+_SEGMENTS_CACHE_MAX = 8
+
+
+def segments_from_cu_seqlens(cu, S, device=None):
+    """Per-row segment bounds for the head_dim 80 pair (int32 [S] each, on
+    `device`): row i of segment [cu[n], cu[n+1]) gets seg_lo[i] = cu[n],
+    seg_hi[i] = cu[n+1]. `cu` is a host list starting at 0 and ending at S,
+    so there is no device sync."""
+    device = torch.device("cpu" if device is None else device)
+    key = (id(cu), S, device)
+    hit = _SEGMENTS_CACHE.get(key)
+    if hit is not None and hit[0] is cu:
+        return hit[1], hit[2]
+    edges = [int(c) for c in cu]
+    if edges[0] != 0 or edges[-1] != S or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"cu_seqlens must rise from 0 to S={S}, got {edges[:4]}..{edges[-1]}")
+    e = torch.tensor(edges, dtype=torch.int32)
+    lens = (e[1:] - e[:-1]).long()
+    both = torch.stack([torch.repeat_interleave(e[:-1], lens),
+                        torch.repeat_interleave(e[1:], lens)]).to(device)
+    seg_lo, seg_hi = both[0].contiguous(), both[1].contiguous()
+    if len(_SEGMENTS_CACHE) >= _SEGMENTS_CACHE_MAX:
+        _SEGMENTS_CACHE.pop(next(iter(_SEGMENTS_CACHE)))
+    _SEGMENTS_CACHE[key] = (cu, seg_lo, seg_hi)
+    return seg_lo, seg_hi
+
+
+def _strided80(t):
+    """t as the kernels read it ([S,H,80], head stride 80, row stride % 8, 16 B
+    aligned): itself when it already is, else a contiguous copy."""
+    ok = (t.stride(2) == 1 and t.stride(1) == t.shape[2] and t.stride(0) % 8 == 0
+          and t.stride(0) >= t.shape[1] * t.shape[2] and t.data_ptr() % 16 == 0)
+    return t if ok else t.contiguous()
+
+
+class _HipVisionAttention(torch.autograd.Function):
+    """vh_attn80_* (csrc/vh_attention80.hip): saves the tensors the forward
+    read, strided views included, and o / lse."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, seg_lo, seg_hi):
+        from .. import hip_lib
+        q, k, v = _strided80(q), _strided80(k), _strided80(v)
+        o, lse = hip_lib.attn80_fwd(q, k, v, scale, seg_lo, seg_hi)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scale = scale
+        ctx.segs = (seg_lo, seg_hi)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        from .. import hip_lib
+        q, k, v, o, lse = ctx.saved_tensors
+        dq, dk, dv = hip_lib.attn80_bwd(q, k, v, o, lse, do, ctx.scale, *ctx.segs)
+        return dq, dk, dv, None, None, None
+
+
+def hip_vision_attention(q, k, v, cu_seqlens, scaling):
+    """[S, H, 80] bf16 non-causal attention inside the segments of the host
+    list cu_seqlens (None: one segment) through the head_dim 80 HIP kernels;
+    q / k / v may be row-strided views (the v slice of the qkv projection).
+    Returns [S, H, 80] contiguous."""
+    if q.shape[-1] != 80:
+        raise ValueError(f"hip_vision_attention: head_dim must be 80, got {q.shape[-1]}")
+    if not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
+        raise ValueError(f"hip_vision_attention: bf16 only, got {q.dtype}")
+    seg_lo = seg_hi = None
+    if cu_seqlens is not None and len(cu_seqlens) > 2:
+        seg_lo, seg_hi = segments_from_cu_seqlens(cu_seqlens, q.shape[0], q.device)
+    return _HipVisionAttention.apply(q, k, v, scaling, seg_lo, seg_hi)
+
+
+def eager_vision_attention(q, k, v, cu_seqlens, scaling):
+    """The torch twin: MASKLESS batched SDPA over runs of equal-length
+    segments, numerically identical to the bool-masked single call, but it
+    keeps torch on the flash / mem-efficient backend (a bool attn_mask forces
+    the math path, which materializes [h, S, S] scores: 5+ GiB and an OOM at
+    the seq-8192 mbs-4 VLM bench shape). [S, H, D] in and out."""
+    cu = cu_seqlens if cu_seqlens is not None else [0, q.shape[0]]
+    H = q.shape[1]
+    out = torch.empty_like(v)            # [S, h, D]
+    i = 0
+    n_seg = len(cu) - 1
+    while i < n_seg:
+        j = i
+        L = cu[i + 1] - cu[i]
+        while j < n_seg and cu[j + 1] - cu[j] == L:
+            j += 1
+        s0, s1, n = cu[i], cu[j], j - i
+        qs = q[s0:s1].reshape(n, L, H, -1).transpose(1, 2)
+        ks = k[s0:s1].reshape(n, L, H, -1).transpose(1, 2)
+        vs = v[s0:s1].reshape(n, L, H, -1).transpose(1, 2)
+        o = F.scaled_dot_product_attention(qs, ks, vs, scale=scaling,
+                                           is_causal=False)
+        out[s0:s1] = o.transpose(1, 2).reshape(n * L, H, -1)
+        i = j
+    return out
+
+
+def vision_attention_forward(q, k, v, cu_seqlens, scaling):
+    """The "hip" implementation of attention/vision_varlen: the head_dim 80
+    pair where it applies, the torch twin for any other head_dim or dtype, off
+    the GPU and under VEOMNI_ATTN_CORE=sdpa (the dispatch policy of
+    hip_attention_forward, not a missing-kernel fallback)."""
+    if (_DEFAULT_CORE == "sdpa" or q.shape[-1] != 80 or not q.is_cuda
+            or q.dtype != torch.bfloat16):
+        return eager_vision_attention(q, k, v, cu_seqlens, scaling)
+    return hip_vision_attention(q, k, v, cu_seqlens, scaling)
+
+
 KERNEL_REGISTRY.register(
     KernelSpec(
         name="hip", op_name="attention", variant="sdpa_with_sp",
@@ -429,3 +546,24 @@ KERNEL_REGISTRY.register(
 # the reference exposes the same callable under this name in HF's
 # ALL_ATTENTION_FUNCTIONS; keep the alias for drop-in callers.
 veomni_flash_attention_2_with_sp = hip_attention_forward
+
+# the vision tower's variant follows the same "attention" entry of the ops
+# config (models/modeling.py bind_ops); "eager" is the twin, registered so
+# the slot resolves it by name as well
+KERNEL_REGISTRY.register(
+    KernelSpec(
+        name="hip", op_name="attention", variant="vision_varlen",
+        factory=lambda: vision_attention_forward,
+        hardware=HardwareRequirement(device_type="gpu"),
+        description="gfx950 head_dim 80 non-causal varlen flash pair "
+                    "(vh_attn80_*); other head dims / dtypes take the twin",
+    )
+)
+KERNEL_REGISTRY.register(
+    KernelSpec(
+        name="eager", op_name="attention", variant="vision_varlen",
+        factory=lambda: eager_vision_attention,
+        hardware=HardwareRequirement(device_type="any"),
+        description="segment-run SDPA loop (the torch twin)",
+    )
+)

@@ -419,11 +419,15 @@ int vh_attn_bwd2_ostrided_bf16(const uint16_t* Q, const uint16_t* K,
  *           with the logit sinks[h] (natural-log domain, not multiplied by
  *           scale) and a zero value vector. LSE includes it. The preprocess
  *           then also writes dsinks[h] = -sum_{b,s} exp(sinks[h] - LSE) *
- *           delta (fp32 [Hq]) through partials (fp32 [B*Hq*S/256] workspace),
+ *           delta (fp32 [Hq]) through partials (fp32 [B*Hq*ceil(S/256)]
+ *           workspace),
  *           summed in a fixed order without atomics; with sinks == NULL it is
  *           vh_attn_bwd_pre_ostrided_bf16. bwd2 needs only the sink-inclusive
  *           lse2.
- * All three: S % 256 == 0, scale > 0, the stride rules above. */
+ * All three: any S >= 1 (S % 256 != 0 launches the tail instantiations: grids
+ * of ceil(S / block), reads of rows >= S redirected to row S-1, stores of
+ * rows >= S skipped; no padding on the caller's side), scale > 0, the stride
+ * rules above. */
 int vh_attn_fwd_win_sink_bf16(const uint16_t* Q, const uint16_t* K,
                               const uint16_t* V, uint16_t* O, float* LSE,
                               int B, int Hq, int Hkv, int64_t S, float scale,
@@ -452,10 +456,11 @@ int vh_attn_bwd2_win_bf16(const uint16_t* Q, const uint16_t* K,
  * [S], monotone, shared by every batch row, so document bounds need B == 1,
  * which the caller enforces; sinks fp32 [Hq], LSE includes the sink).
  * fwd: O, LSE [B,Hq,S] fp32. bwd_pre: delta, lse2 = LSE*log2e [B*Hq*S] and,
- * with sinks, dsinks [Hq] through partials (fp32 [B*Hq*S/256] workspace),
+ * with sinks, dsinks [Hq] through partials (fp32 [B*Hq*ceil(S/256)] workspace),
  * summed in a fixed order without atomics. bwd2: dQ [B,Hq,S,64], dK / dV
  * [B,Hkv,S,64], each written once; lo and hi both or neither.
- * All three: S % 256 == 0; fwd and bwd2: scale > 0, Hq % Hkv == 0. */
+ * All three: any S >= 1 (tail instantiations for S % 256 != 0, as the D = 128
+ * win_sink set); fwd and bwd2: scale > 0, Hq % Hkv == 0. */
 int vh_attn64_fwd_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
                        uint16_t* O, float* LSE, int B, int Hq, int Hkv,
                        int64_t S, float scale, const int32_t* lo,

@@ -4,7 +4,10 @@
 // (ref ops/kernels/attention/flash.py:153-301) for the packed causal path.
 //
 // Structure (guide cdna_hip_programming.md Appendix B, swapped-QK^T design):
-//   grid (S/256, B*Hq); block = 8 waves (512 thr), wave w owns 32 q rows.
+//   grid (ceil(S/256), B*Hq); block = 8 waves (512 thr), wave w owns 32 q
+//   rows. S % 256 != 0 (win_sink entry points only) launches the TAIL
+//   instantiations of the forward, pre4_sink, dkv and dq kernels: same tiling,
+//   reads of rows >= S redirected to row S-1, stores of rows >= S skipped.
 //   Q fragments live in registers (tile-invariant); K and V tiles
 //   ([64 kv][128 d]) are double-buffered and both filled by glds straight
 //   into LDS, issued before the tile's MFMA phase (T14): K with a
@@ -147,7 +150,15 @@ __host__ inline OStrides head_major(int Hq, int64_t S) {
 // <= DEFER_THR) and a negligible one is scaled away by the first rescale.
 // LSE includes the sink, which is all the backward kernels need: their
 // P = exp2(s*scale2 - lse2) is then the sink-inclusive probability.
-template <bool DOC, bool SINK>
+// TAIL (S % 256 != 0, reached through the win_sink entry points; every kernel
+// of this file that has the flag): the grid is ceil(S / block) and a lane
+// whose row is >= S reads, and is masked as, row S-1; its results are not
+// stored. The kv loop ends at the tile that holds row S-1; staged rows >= S
+// are fetched from row S-1 (lane offsets clamped to the tile-local index of
+// row S-1), so they are copies of key S-1, which lies above the diagonal of
+// every row and is hidden by the masked body. DESIGN.md, "Ragged tails in the
+// causal pairs".
+template <bool DOC, bool SINK, bool TAIL>
 __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
@@ -180,7 +191,11 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
   bf16_t* Ob = O + b * os.sb + hq * os.sh;
   float* Lb = LSE + ((int64_t)b * Hq + hq) * S;
 
-  const int64_t q_global = (int64_t)qb * QB + wave * WQ + col;
+  const int64_t w0r = (int64_t)qb * QB + wave * WQ;  // the wave's first q row
+  // rows the wave and the lane compute (TAIL: clamped to S-1)
+  const int64_t w0 = TAIL ? min(w0r, S - 1) : w0r;
+  const int64_t w1 = TAIL ? min(w0r + WQ - 1, S - 1) : w0r + WQ - 1;
+  const int64_t q_global = TAIL ? min(w0r + col, S - 1) : w0r + col;
   const float scale2 = scale * 1.4426950408889634f;  // log2(e)
 
   // varlen: this lane's document start, and the wave/block minima (doc_start
@@ -188,7 +203,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
   int ds_l = 0, ds_wave = 0, t0 = 0;
   if (DOC) {
     ds_l = doc_start[q_global];
-    ds_wave = doc_start[(int64_t)qb * QB + wave * WQ];
+    ds_wave = doc_start[w0];
     t0 = doc_start[(int64_t)qb * QB] / KB;
   }
 
@@ -215,6 +230,19 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     ksrc[i] = (uint32_t)(row * DH + (kswz(row, colb) >> 1));
     klds[i] = base >> 1;
   }
+  // TAIL: the tile that holds row S-1 and the tile-local index of that row;
+  // the K lane offsets of that tile (the swizzle stays the destination row's)
+  const int t_tail = TAIL ? (int)((S - 1) / KB) : 0;
+  const int rmax = TAIL ? (int)(S - 1) - t_tail * KB : 0;
+  uint32_t ksrc_t[2] = {0, 0};
+  if (TAIL) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int o = i * 8192 + wave * 1024 + lane * 16;
+      const int row = o >> 8;
+      ksrc_t[i] = (uint32_t)(min(row, rmax) * DH + (kswz(row, o & 255) >> 1));
+    }
+  }
   f32x16 oacc[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) oacc[d] = f32x16{};
@@ -225,7 +253,9 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     l_run = 1.f;
   }
 
-  const int t_max = (int)(((int64_t)qb * QB + QB - 1) / KB);  // inclusive
+  // inclusive; TAIL: no tile past the one that holds row S-1
+  const int t_max = TAIL ? min((int)(((int64_t)qb * QB + QB - 1) / KB), t_tail)
+                         : (int)(((int64_t)qb * QB + QB - 1) / KB);
 
   // ---- per-lane LDS read addresses of the current buffer, carried across
   // the loop and flipped to the other buffer once per tile; sub / mch select
@@ -258,7 +288,9 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
   {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      glds16a(Kb + (int64_t)t0 * KB * DH + ksrc[i], kt(0) + klds[i]);
+      glds16a(Kb + (int64_t)t0 * KB * DH +
+                  ((TAIL && t0 == t_tail) ? ksrc_t[i] : ksrc[i]),
+              kt(0) + klds[i]);
     // glds fill of the L16 V image: window win = wave*2+u covers 4 kv rows
     // (1024 B, lane-linear dest); lane sources pair p = P(slot ^ (kv&15))
 #pragma unroll
@@ -267,7 +299,8 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
       const int kvr = win * 4 + (lane >> 4);
       const int pp0 = (lane & 15) ^ (kvr & 15);
       const int pg = ((pp0 & 3) << 2) | (pp0 >> 2);
-      glds16a(Vb + (int64_t)t0 * KB * DH + (uint32_t)(kvr * DH + pg * 8),
+      const int kvs = (TAIL && t0 == t_tail) ? min(kvr, rmax) : kvr;
+      glds16a(Vb + (int64_t)t0 * KB * DH + (uint32_t)(kvs * DH + pg * 8),
               vt(0) + win * 512);
     }
   }
@@ -279,7 +312,8 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     if (t < t_max) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
-        glds16a(Kb + (int64_t)(t + 1) * KB * DH + ksrc[i],
+        glds16a(Kb + (int64_t)(t + 1) * KB * DH +
+                    ((TAIL && t + 1 == t_tail) ? ksrc_t[i] : ksrc[i]),
                 kt(cur ^ 1) + klds[i]);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -287,17 +321,18 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
         const int kvr = win * 4 + (lane >> 4);
         const int pp0 = (lane & 15) ^ (kvr & 15);
         const int pg = ((pp0 & 3) << 2) | (pp0 >> 2);
+        const int kvs = (TAIL && t + 1 == t_tail) ? min(kvr, rmax) : kvr;
         glds16a(Vb + (int64_t)(t + 1) * KB * DH +
-                    (uint32_t)(kvr * DH + pg * 8),
+                    (uint32_t)(kvs * DH + pg * 8),
                 vt(cur ^ 1) + win * 512);
       }
     }
 
-    const bool diag = ((int64_t)(t + 1) * KB) > ((int64_t)qb * QB + wave * WQ);
+    const bool diag = ((int64_t)(t + 1) * KB) > w0;
     // causal skip: every kv in this tile is beyond every q of this wave
     // (varlen adds: or before every document of this wave)
     const bool live =
-        ((int64_t)t * KB <= (int64_t)qb * QB + wave * WQ + (WQ - 1)) &&
+        ((int64_t)t * KB <= w1) &&
         (!DOC || (int64_t)(t + 1) * KB > ds_wave);
 
     // One 32-kv subtile. MASK is a compile-time tag: the masked body applies
@@ -436,15 +471,16 @@ __global__ __launch_bounds__(512, 2) void k_attn_fwd(
     int qr = (r & 3) + 8 * (r >> 2) + 4 * half;
     float l_r = __shfl(l_run, qr, 32);
     float inv = 1.0f / l_r;
-    int64_t qg = (int64_t)qb * QB + wave * WQ + qr;
+    int64_t qg = w0r + qr;
+    if (TAIL && qg >= S) continue;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       Ob[qg * os.sr + d * 32 + col] = f2bf(oacc[d][r] * inv);
     }
   }
-  if (half == 0) {
+  if (half == 0 && (!TAIL || w0r + col < S)) {
     // back to the natural-log domain: LSE = ln2 * (m2 + log2(l))
-    Lb[q_global] = 0.6931471805599453f * (m_run + __log2f(l_run));
+    Lb[w0r + col] = 0.6931471805599453f * (m_run + __log2f(l_run));
   }
 }
 
@@ -465,15 +501,17 @@ static int attn_fwd_launch(const uint16_t* Q, const uint16_t* K,
                            int Hq, int Hkv, int64_t S, float scale,
                            const int32_t* doc_start, OStrides os,
                            void* stream, const float* sinks = nullptr,
-                           bool shared_bounds = false) {
+                           bool shared_bounds = false, bool any_s = false) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  VH_CHECK(S % QB == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(S > 0 && B > 0 && Hq > 0 && Hkv > 0, "B, Hq, Hkv, S must be > 0");
+  VH_CHECK(any_s || S % QB == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(S * DH < (1ll << 31), "S too large for 32-bit tile offsets");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
   VH_CHECK(doc_start == nullptr || B == 1 || shared_bounds,
            "varlen requires packed B == 1");
   // a softmax scale is positive; zero or negative is a caller's mistake
   VH_CHECK(scale > 0, "scale must be > 0 (got %g)", (double)scale);
-  dim3 grid((uint32_t)(S / QB), (uint32_t)(B * Hq));
+  dim3 grid((uint32_t)((S + QB - 1) / QB), (uint32_t)(B * Hq));
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, dim3(512), 65536, s,
                        reinterpret_cast<const bf16_t*>(Q),
@@ -482,12 +520,22 @@ static int attn_fwd_launch(const uint16_t* Q, const uint16_t* K,
                        reinterpret_cast<bf16_t*>(O), LSE, doc_start, B, Hq,
                        Hkv, S, scale, os, sinks);
   };
-  if (sinks) {
-    if (doc_start) launch(k_attn_fwd<true, true>);
-    else launch(k_attn_fwd<false, true>);
+  if (S % QB == 0) {
+    if (sinks) {
+      if (doc_start) launch(k_attn_fwd<true, true, false>);
+      else launch(k_attn_fwd<false, true, false>);
+    } else {
+      if (doc_start) launch(k_attn_fwd<true, false, false>);
+      else launch(k_attn_fwd<false, false, false>);
+    }
   } else {
-    if (doc_start) launch(k_attn_fwd<true, false>);
-    else launch(k_attn_fwd<false, false>);
+    if (sinks) {
+      if (doc_start) launch(k_attn_fwd<true, true, true>);
+      else launch(k_attn_fwd<false, true, true>);
+    } else {
+      if (doc_start) launch(k_attn_fwd<true, false, true>);
+      else launch(k_attn_fwd<false, false, true>);
+    }
   }
   VH_HIP(hipGetLastError());
   return 0;
@@ -526,7 +574,7 @@ extern "C" int vh_attn_fwd_win_sink_bf16(
   if (int rc = check_ostrides(O, o_sb, o_sh, o_sr)) return rc;
   return attn_fwd_launch(Q, K, V, O, LSE, B, Hq, Hkv, S, scale, lo,
                          OStrides{o_sb, o_sh, o_sr}, stream, sinks,
-                         /*shared_bounds=*/true);
+                         /*shared_bounds=*/true, /*any_s=*/true);
 }
 
 // ============================================================================
@@ -626,6 +674,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pre4(
 // (part[bh*nblk + blk]); the sums inside a block and in k_attn_dsinks_finish
 // run in a fixed order and use no atomics, so dsinks is the same from run to
 // run and for every O/dO layout.
+// TAIL: grid ceil(S/256); a row >= S reads row S-1, stores nothing and adds 0.
+template <bool TAIL>
 __global__ __launch_bounds__(256) void k_attn_bwd_pre4_sink(
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O,
     const float* __restrict__ LSE, const float* __restrict__ sinks,
@@ -642,7 +692,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pre4_sink(
   const float sink = sinks[hq];
   float gacc = 0.f;   // this 16-lane group's share, the same in its lanes
   for (int it = 0; it < 16; ++it) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + it * 16 + wave * 4 + sub;
+    const int64_t sr = (int64_t)blockIdx.x * 256 + it * 16 + wave * 4 + sub;
+    const bool ok = !TAIL || sr < S;
+    const int64_t s = TAIL ? min(sr, S - 1) : sr;
     const int64_t r = bh * S + s;
     const int64_t off = base + s * os.sr;
     bf16x8 a = reinterpret_cast<const bf16x8*>(dO + off)[cl];
@@ -653,11 +705,11 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pre4_sink(
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
     const float lse = LSE[r];
-    if (cl == 0) {
+    if (cl == 0 && ok) {
       delta[r] = acc;
       lse2[r] = lse * 1.4426950408889634f;
     }
-    gacc += expf(sink - lse) * acc;
+    gacc += ok ? expf(sink - lse) * acc : 0.f;
   }
   const float g0 = __shfl(gacc, 0, kWave), g1 = __shfl(gacc, 16, kWave);
   const float g2 = __shfl(gacc, 32, kWave), g3 = __shfl(gacc, 48, kWave);
@@ -719,7 +771,13 @@ __global__ void k_attn_dsinks_finish(const float* __restrict__ part,
 //     `diag`: with and without the per-score mask select.
 // LDS 64.75 KB: K/V strips 2x16 K + Q/dO tiles 2x16 K + 768 B of per-row
 // scalars -> still 2 blocks/CU (160 KiB).
-template <bool DOC>
+// TAIL: strip rows >= S stage K / V row S-1 and are not stored; the q tile
+// that holds row S-1 is staged with clamped sources (Q, dO, lse2, delta,
+// doc_start; the lane offsets are rebuilt per tile here anyway, so the clamp
+// is one v_min against the tile's scalar S-1-q0t) and its rows >= S get
+// P = dS = 0 through a row < S term in the masked body, which every quadrant
+// that reaches S takes.
+template <bool DOC, bool TAIL>
 __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
@@ -763,12 +821,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
     int o = i * 4096 + tid * 16;
     int row = o >> 8;
     int colb = o & 255;
+    const int64_t kvs = TAIL ? min(kv0 + row, S - 1) : kv0 + row;
     *reinterpret_cast<bf16x8*>(
         reinterpret_cast<char*>(krow) + row * 256 + kswz(row, colb)) =
-        *reinterpret_cast<const bf16x8*>(Kb + (kv0 + row) * DH + (colb >> 1));
+        *reinterpret_cast<const bf16x8*>(Kb + kvs * DH + (colb >> 1));
     *reinterpret_cast<bf16x8*>(
         reinterpret_cast<char*>(vrow) + row * 256 + kswz(row, colb)) =
-        *reinterpret_cast<const bf16x8*>(Vb + (kv0 + row) * DH + (colb >> 1));
+        *reinterpret_cast<const bf16x8*>(Vb + kvs * DH + (colb >> 1));
   }
 
   f32x16 dv_acc[4], dk_acc[4];
@@ -780,11 +839,14 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
 
   const float scale2 = scale * 1.4426950408889634f;
   const int qt0 = (int)(kv0 / 64);     // 64-row q tiles
-  int qtn = (int)(S / 64);
+  int qtn = (int)((S + (TAIL ? 63 : 0)) / 64);
   int de_wave = 0;
   if (DOC) {
-    qtn = (doc_end[kv0 + 63] + 63) / 64;          // block-uniform end
-    de_wave = doc_end[kv0 + kvslice * 32 + 31];   // wave-live bound
+    const int64_t j_b = TAIL ? min(kv0 + 63, S - 1) : kv0 + 63;
+    const int64_t j_w =
+        TAIL ? min(kv0 + kvslice * 32 + 31, S - 1) : kv0 + kvslice * 32 + 31;
+    qtn = (doc_end[j_b] + 63) / 64;               // block-uniform end
+    de_wave = doc_end[j_w];                       // wave-live bound
   }
 
   // single flattened loop over (head g, q tile): one live address chain —
@@ -803,6 +865,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
       const float* lseb = lse2 + ((int64_t)b * Hq + hq) * S;
       const int64_t q0t = (int64_t)qt * 64;
       const int64_t q0 = q0t + qsub * 32;   // this wave's 32-q subtile
+      // TAIL: tile-local index of row S-1 (>= 63 on every tile but the last)
+      const int rmax = TAIL ? (int)min(S - 1 - q0t, (int64_t)63) : 63;
       // stage the Q / dO tiles [64 q][128 d]: glds fill of the L16 image.
       // Window win = wave*4+u covers 4 q rows (1024 B, lane-linear dest);
       // lane sources pair p = P(slot ^ (q&15)) — zero VGPR staging, zero
@@ -814,7 +878,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
         const int pp0 = (lane & 15) ^ (qrow & 15);
         const int pg = ((pp0 & 3) << 2) | (pp0 >> 2);
         // uniform tile base + 32-bit lane offset (scalar-base addressing)
-        const uint32_t loff = (uint32_t)(qrow * DH + pg * 8);
+        const uint32_t loff =
+            (uint32_t)((TAIL ? min(qrow, rmax) : qrow) * DH + pg * 8);
         glds16a(Qb + q0t * DH + loff, qtr + win * 512);
       }
       // dO rows are dos.sr elements apart, so its lane offsets are its own.
@@ -829,20 +894,22 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
         asm volatile("" : "+v"(qrow));
         const uint32_t pp0 = (lane & 15) ^ (qrow & 15);
         const uint32_t pg = ((pp0 & 3) << 2) | (pp0 >> 2);
-        glds16a(dOb + q0t * dos.sr + (uint32_t)(qrow * (uint32_t)dos.sr + pg * 8),
+        const uint32_t qsrc = TAIL ? min(qrow, (uint32_t)rmax) : qrow;
+        glds16a(dOb + q0t * dos.sr + (uint32_t)(qsrc * (uint32_t)dos.sr + pg * 8),
                 dotr + win * 512);
       }
       // the tile's 64 lse2 / delta (and, varlen, doc_start) values go to LDS
       // next to the images: one dword per lane, waves 0 / 1 / 2
-      if (wave == 0) glds4(lseb + q0t + (uint32_t)lane, stat);
-      else if (wave == 1) glds4(delb + q0t + (uint32_t)lane, stat + 64);
+      const uint32_t sl = TAIL ? (uint32_t)min(lane, rmax) : (uint32_t)lane;
+      if (wave == 0) glds4(lseb + q0t + sl, stat);
+      else if (wave == 1) glds4(delb + q0t + sl, stat + 64);
       else if (DOC && wave == 2)
-        glds4(doc_start + q0t + (uint32_t)lane, stat + 128);
+        glds4(doc_start + q0t + sl, stat + 128);
       __syncthreads();
 
       const bool live = ((q0 + 31) >= (kv0 + kvslice * 32)) &&
-                        (!DOC || q0 < de_wave);
-      const bool diag = (q0 < kv0 + 64);
+                        (!DOC || q0 < de_wave) && (!TAIL || q0 < S);
+      const bool diag = (q0 < kv0 + 64) || (TAIL && q0 + 31 >= S);
       if (live) {
         f32x16 s2 = f32x16{}, dp2 = f32x16{};
 #pragma unroll
@@ -879,6 +946,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
           const int kvl = kvslice * 32 + col;
           const int c_lim = kvl - (int)(q0 - kv0) - 4 * half;
           const int kv_abs = (int)kv0 + kvl;
+          // TAIL: q row q0 + idx + 4*half is >= S
+          const int r_lim = (int)(S - q0) - 4 * half;
           // per-score softmax scalars: score r belongs to q row
           // (r&3) + 8*(r>>2) + 4*half of the subtile, i.e. four runs of four
           // consecutive rows -> one b128 broadcast read per run and quantity.
@@ -912,6 +981,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
                   const int idx = i + 8 * j;
                   bool masked = idx < c_lim;
                   if (DOC) masked = masked || (kv_abs < ds_q[i]);
+                  if (TAIL) masked = masked || (idx >= r_lim);
                   pp = masked ? 0.f : pp;
                 }
                 pv[rr] = pp;
@@ -1000,6 +1070,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
       _Pragma("unroll") for (int r = 0; r < 16; ++r) {                        \
         int kvr = (r & 3) + 8 * (r >> 2) + 4 * half;                          \
         int64_t kvg = kv0 + kvslice * 32 + kvr;                               \
+        if (TAIL && kvg >= S) continue;                                       \
         _Pragma("unroll") for (int d = 0; d < 4; ++d) DST[kvg * DH + d * 32 + \
                                                           col] =             \
             f2bf(ACC[d][r]);                                                  \
@@ -1025,7 +1096,10 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dkv_g(
 // pack + partner-quad exchange, dQ chain (8 MFMA). The K/V/K^T read
 // addresses stay base-plus-tile-offset adds: with one 32-row tile per
 // iteration a carried, flipped address costs the same one add per base.
-template <bool DOC>
+// TAIL: as the forward: rows >= S compute row S-1 and are not stored; the kv
+// loop ends at the tile that holds row S-1, whose staged rows >= S come from
+// row S-1 (per-tile clamp of the rebuilt lane offsets).
+template <bool DOC, bool TAIL>
 __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
@@ -1059,7 +1133,11 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
   bf16_t* dQb = dQ + (((int64_t)b * Hq + hq) * S) * DH;
 
   const int64_t q0b = (int64_t)qb * 128;
-  const int64_t q_l = q0b + wave * 32 + col;   // this lane's q row
+  const int64_t w0r = q0b + wave * 32;         // the wave's first q row
+  // rows the wave and the lane compute (TAIL: clamped to S-1)
+  const int64_t w0 = TAIL ? min(w0r, S - 1) : w0r;
+  const int64_t w1 = TAIL ? min(w0r + 31, S - 1) : w0r + 31;
+  const int64_t q_l = TAIL ? min(w0r + col, S - 1) : w0r + col;
 
   // the wave's Q/dO rows and lse/delta are fixed for the whole kernel
   bf16frag qrow[8], dorow[8];
@@ -1075,7 +1153,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
   int ds_l = 0, ds_wave = 0, kvt_begin = 0;
   if (DOC) {
     ds_l = doc_start[q_l];
-    ds_wave = doc_start[q0b + wave * 32];
+    ds_wave = doc_start[w0];
     kvt_begin = doc_start[q0b] / 32;
   }
 
@@ -1083,7 +1161,9 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
 #pragma unroll
   for (int d = 0; d < 4; ++d) dq4[d] = f32x16{};
 
-  const int kvtn = (int)((q0b + 128) / 32);
+  // exclusive; TAIL: no tile past the one that holds row S-1
+  const int kvtn = TAIL ? (int)min((q0b + 128) / 32, (S - 1) / 32 + 1)
+                        : (int)((q0b + 128) / 32);
   // glds one whole tile set (krow/vrow kswz + ktr L16) into buffer BF
 #define VH_DQ_STAGE(KVT2, BF)                                                  \
   {                                                                            \
@@ -1094,9 +1174,12 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
       const int row_ = win_ * 4 + (lane >> 4);                                 \
       const int c16_ = (lane & 15) ^ (row_ & 15);                              \
       const int pg_ = (((c16_ & 3) << 2) | (c16_ >> 2));                       \
+      /* TAIL: rows >= S of the tile fetch row S-1 */                          \
+      const int rs_ =                                                          \
+          TAIL ? min(row_, (int)min(S - 1 - kv0_, (int64_t)31)) : row_;        \
       /* uniform tile base + 32-bit lane offset (scalar-base addressing) */    \
-      const uint32_t lo_ = (uint32_t)(row_ * DH + c16_ * 8);                   \
-      const uint32_t lp_ = (uint32_t)(row_ * DH + pg_ * 8);                    \
+      const uint32_t lo_ = (uint32_t)(rs_ * DH + c16_ * 8);                    \
+      const uint32_t lp_ = (uint32_t)(rs_ * DH + pg_ * 8);                     \
       glds16a(Kb + kv0_ * DH + lo_,                                            \
               reinterpret_cast<bf16_t*>(kb_) + win_ * 512);                    \
       glds16a(Vb + kv0_ * DH + lo_,                                            \
@@ -1116,9 +1199,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
     const bf16_t* ktr = reinterpret_cast<bf16_t*>(base_ + 16384);
     if (kvt + 1 < kvtn) VH_DQ_STAGE(kvt + 1, cur ^ 1);
 
-    const bool live = (kvt0 <= q0b + wave * 32 + 31) &&
-                      (!DOC || kvt0 + 31 >= ds_wave);
-    const bool diag = (kvt0 + 31 >= q0b + wave * 32);
+    const bool live = (kvt0 <= w1) && (!DOC || kvt0 + 31 >= ds_wave);
+    const bool diag = (kvt0 + 31 >= w0);
 
     if (live) {
       // or1: C = [kv regs][q lanes]; s1 = mfma(K, Q)
@@ -1214,7 +1296,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_bwd_dq(
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int qr = (r & 3) + 8 * (r >> 2) + 4 * half;
-    int64_t qg = q0b + wave * 32 + qr;
+    int64_t qg = w0r + qr;
+    if (TAIL && qg >= S) continue;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       dQb[qg * DH + d * 32 + col] = f2bf(dq4[d][r]);
@@ -1260,16 +1343,16 @@ extern "C" int vh_attn_bwd_pre_ostrided_bf16(
 
 /* vh_attn_bwd_pre_ostrided_bf16 that also returns the attention-sink
  * gradient. sinks (nullable, fp32 [Hq]): with it, dsinks (fp32 [Hq]) is
- * written and partials (fp32 [B*Hq*S/256], workspace) is used; LSE must be
+ * written and partials (fp32 [B*Hq*ceil(S/256)], workspace) is used; LSE must be
  * the sink-inclusive one of vh_attn_fwd_win_sink_bf16. Without it the call
- * is vh_attn_bwd_pre_ostrided_bf16. S % 256 == 0. */
+ * is vh_attn_bwd_pre_ostrided_bf16. Any S >= 1. */
 extern "C" int vh_attn_bwd_pre_sink_bf16(
     const uint16_t* dO, const uint16_t* O, const float* LSE,
     const float* sinks, float* delta, float* lse2, float* dsinks,
     float* partials, int B, int Hq, int64_t S, int64_t o_sb, int64_t o_sh,
     int64_t o_sr, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  VH_CHECK(S > 0 && S % 256 == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(S > 0, "S must be > 0");
   VH_CHECK(B > 0 && Hq > 0, "B, Hq must be > 0");
   if (sinks == nullptr)
     return vh_attn_bwd_pre_ostrided_bf16(dO, O, LSE, delta, lse2, B, Hq, S,
@@ -1278,11 +1361,15 @@ extern "C" int vh_attn_bwd_pre_sink_bf16(
            "sinks need the dsinks output and the partials workspace");
   if (int rc = check_ostrides(dO, o_sb, o_sh, o_sr)) return rc;
   if (int rc = check_ostrides(O, o_sb, o_sh, o_sr)) return rc;
-  const int nblk = (int)(S / 256);
-  hipLaunchKernelGGL(k_attn_bwd_pre4_sink, dim3(nblk, (uint32_t)(B * Hq)),
-                     dim3(256), 0, s, reinterpret_cast<const bf16_t*>(dO),
-                     reinterpret_cast<const bf16_t*>(O), LSE, sinks, delta,
-                     lse2, partials, S, Hq, OStrides{o_sb, o_sh, o_sr});
+  const int nblk = (int)((S + 255) / 256);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(nblk, (uint32_t)(B * Hq)), dim3(256), 0, s,
+                       reinterpret_cast<const bf16_t*>(dO),
+                       reinterpret_cast<const bf16_t*>(O), LSE, sinks, delta,
+                       lse2, partials, S, Hq, OStrides{o_sb, o_sh, o_sr});
+  };
+  if (S % 256 == 0) launch(k_attn_bwd_pre4_sink<false>);
+  else launch(k_attn_bwd_pre4_sink<true>);
   VH_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_attn_dsinks_finish, dim3((Hq + 63) / 64), dim3(64), 0,
                      s, partials, dsinks, B, Hq, nblk);
@@ -1297,16 +1384,18 @@ static int attn_bwd2_launch(const uint16_t* Q, const uint16_t* K,
                             int Hq, int Hkv, int64_t S, float scale,
                             const int32_t* doc_start, const int32_t* doc_end,
                             OStrides dos, void* stream,
-                            bool shared_bounds = false) {
+                            bool shared_bounds = false, bool any_s = false) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  VH_CHECK(S % 128 == 0, "S %% 128 != 0");
+  VH_CHECK(S > 0 && B > 0 && Hq > 0 && Hkv > 0, "B, Hq, Hkv, S must be > 0");
+  VH_CHECK(any_s || S % 128 == 0, "S %% 128 != 0");
+  VH_CHECK(S * DH < (1ll << 31), "S too large for 32-bit tile offsets");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
   VH_CHECK((doc_start == nullptr) == (doc_end == nullptr),
            "doc_start/doc_end must be passed together");
   VH_CHECK(doc_start == nullptr || B == 1 || shared_bounds,
            "varlen requires packed B == 1");
-  dim3 grid_kv((uint32_t)(S / 64), (uint32_t)(B * Hkv));
-  dim3 grid_q((uint32_t)(S / 128), (uint32_t)(B * Hq));
+  dim3 grid_kv((uint32_t)((S + 63) / 64), (uint32_t)(B * Hkv));
+  dim3 grid_q((uint32_t)((S + 127) / 128), (uint32_t)(B * Hq));
   auto launch_dkv = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid_kv, dim3(256), 65536 + 768, s,
                        reinterpret_cast<const bf16_t*>(Q),
@@ -1326,11 +1415,23 @@ static int attn_bwd2_launch(const uint16_t* Q, const uint16_t* K,
                        reinterpret_cast<bf16_t*>(dQ), doc_start, B, Hq, Hkv,
                        S, scale, dos);
   };
-  if (doc_start) launch_dkv(k_attn_bwd_dkv_g<true>);
-  else launch_dkv(k_attn_bwd_dkv_g<false>);
+  // only the win set (any_s) launches the TAIL instantiations
+  const bool tail = any_s && S % 256 != 0;
+  if (tail) {
+    if (doc_start) launch_dkv(k_attn_bwd_dkv_g<true, true>);
+    else launch_dkv(k_attn_bwd_dkv_g<false, true>);
+  } else {
+    if (doc_start) launch_dkv(k_attn_bwd_dkv_g<true, false>);
+    else launch_dkv(k_attn_bwd_dkv_g<false, false>);
+  }
   VH_HIP(hipGetLastError());
-  if (doc_start) launch_dq(k_attn_bwd_dq<true>);
-  else launch_dq(k_attn_bwd_dq<false>);
+  if (tail) {
+    if (doc_start) launch_dq(k_attn_bwd_dq<true, true>);
+    else launch_dq(k_attn_bwd_dq<false, true>);
+  } else {
+    if (doc_start) launch_dq(k_attn_bwd_dq<true, false>);
+    else launch_dq(k_attn_bwd_dq<false, false>);
+  }
   VH_HIP(hipGetLastError());
   return 0;
 }
@@ -1369,17 +1470,16 @@ extern "C" int vh_attn_bwd2_ostrided_bf16(
  * hi[j] the exclusive end of the rows that see key j, both monotone
  * non-decreasing with lo[q] <= q < hi[q] <= S; B > 1 allowed. delta and lse2
  * come from vh_attn_bwd_pre_sink_bf16: with a sink-inclusive LSE the two
- * kernels need nothing else for sinks. S % 256 == 0. */
+ * kernels need nothing else for sinks. Any S >= 1. */
 extern "C" int vh_attn_bwd2_win_bf16(
     const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* dO,
     const float* delta, const float* lse2, uint16_t* dQ, uint16_t* dK,
     uint16_t* dV, int B, int Hq, int Hkv, int64_t S, float scale,
     const int32_t* lo, const int32_t* hi, int64_t do_sb, int64_t do_sh,
     int64_t do_sr, void* stream) {
-  VH_CHECK(S % 256 == 0, "S %% 256 != 0 (pad the sequence)");
   VH_CHECK(scale > 0, "scale must be > 0 (got %g)", (double)scale);
   if (int rc = check_ostrides(dO, do_sb, do_sh, do_sr)) return rc;
   return attn_bwd2_launch(Q, K, V, dO, delta, lse2, dQ, dK, dV, B, Hq, Hkv, S,
                           scale, lo, hi, OStrides{do_sb, do_sh, do_sr}, stream,
-                          /*shared_bounds=*/true);
+                          /*shared_bounds=*/true, /*any_s=*/true);
 }

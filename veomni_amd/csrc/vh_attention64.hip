@@ -38,6 +38,8 @@
 // fetches chunk (i%8) ^ g(row) of that row. No staging registers, no ds_write.
 //
 // Kernels, LDS, waves, occupancy (registers: profiles/attn_d64_microbench.md):
+//   (grids are ceil(S / block); S % 256 != 0 launches the TAIL instantiations:
+//   same tiling, reads of rows >= S redirected to row S-1, stores guarded)
 //   k_attn64_fwd      grid (S/256, B*Hq), 8 waves x 32 q rows, 128-row kv
 //                     tiles, K and V 16 KiB each, double buffered: 64 KiB.
 //                     LDS would admit 2 blocks per CU; the two live score
@@ -109,6 +111,14 @@ __device__ __forceinline__ uint32_t img_src(int win, int lane) {
   return (uint32_t)(row * DH + (((lane & 7) ^ rperm(row)) << 3));
 }
 
+// img_src for the tile that holds row S-1: rows past `rmax` (the tile-local
+// index of row S-1) fetch row rmax instead; the chunk permutation stays the
+// destination row's, so the image keeps its layout
+__device__ __forceinline__ uint32_t img_src_tail(int win, int lane, int rmax) {
+  const int row = win * 8 + (lane >> 3);
+  return (uint32_t)(min(row, rmax) * DH + (((lane & 7) ^ rperm(row)) << 3));
+}
+
 __device__ __forceinline__ uint32_t swap32_u(uint32_t v, int half) {
   auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
   return half ? (uint32_t)r[0] : (uint32_t)r[1];
@@ -159,7 +169,13 @@ __device__ __forceinline__ void tr_offsets(int lane, int dblk, int& a0, int& a1)
 // ============================================================================
 // Forward
 // ============================================================================
-template <bool DOC, bool SINK>
+// TAIL (S % 256 != 0, every kernel of this file): the grid is ceil(S / block)
+// and a lane whose row is >= S reads, and is masked as, row S-1; its results
+// are not stored. The kv loop ends at the tile that holds row S-1, whose
+// staging sources are clamped the same way (img_src_tail): its keys >= S are
+// copies of key S-1 and lie above the diagonal of every row, so the masked
+// body hides them. DESIGN.md, "Ragged tails in the causal pairs".
+template <bool DOC, bool SINK, bool TAIL>
 __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, bf16_t* __restrict__ O,
@@ -185,8 +201,12 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
   bf16_t* Ob = O + (((int64_t)b * Hq + hq) * S) * DH;
   float* Lb = LSE + ((int64_t)b * Hq + hq) * S;
 
-  const int w0 = qb * QB + wave * WQ;          // the wave's first q row
-  const int q_row = w0 + col;                  // this lane's q row
+  const int w0r = qb * QB + wave * WQ;         // the wave's first q row
+  const int sm1 = (int)S - 1;
+  // rows the wave and the lane compute (TAIL: clamped to S-1)
+  const int w0 = TAIL ? min(w0r, sm1) : w0r;
+  const int w1 = TAIL ? min(w0r + WQ - 1, sm1) : w0r + WQ - 1;
+  const int q_row = TAIL ? min(w0r + col, sm1) : w0r + col;
   const float scale2 = scale * LOG2E;
 
   // bounds: this lane's, and the wave's smallest / largest (lo is monotone)
@@ -194,7 +214,7 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
   if (DOC) {
     lo_l = lo[q_row];
     lo_w0 = __builtin_amdgcn_readfirstlane(lo[w0]);
-    lo_w1 = __builtin_amdgcn_readfirstlane(lo[w0 + WQ - 1]);
+    lo_w1 = __builtin_amdgcn_readfirstlane(lo[w1]);
     t0 = lo[qb * QB] / KB;
   }
 
@@ -209,6 +229,14 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
   uint32_t ssrc[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) ssrc[u] = img_src(wave * 2 + u, lane);
+  // TAIL: the lane offsets of the tile that holds row S-1
+  const int t_tail = TAIL ? sm1 / KB : 0;
+  uint32_t ssrc_t[2] = {0, 0};
+  if (TAIL) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      ssrc_t[u] = img_src_tail(wave * 2 + u, lane, sm1 - t_tail * KB);
+  }
   auto stage = [&](int t, int buf) __attribute__((always_inline)) {
     const bf16_t* kg = Kb + (int64_t)t * KB * DH;
     const bf16_t* vg = Vb + (int64_t)t * KB * DH;
@@ -216,8 +244,9 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
     bf16_t* vl = reinterpret_cast<bf16_t*>(smem + 32768 + buf * 16384);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      glds16a(kg + ssrc[u], kl + (wave * 2 + u) * 512);
-      glds16a(vg + ssrc[u], vl + (wave * 2 + u) * 512);
+      const uint32_t so = (TAIL && t == t_tail) ? ssrc_t[u] : ssrc[u];
+      glds16a(kg + so, kl + (wave * 2 + u) * 512);
+      glds16a(vg + so, vl + (wave * 2 + u) * 512);
     }
   };
 
@@ -249,7 +278,9 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
   }
   int flip = 16384;
 
-  const int t_max = (qb * QB + QB - 1) / KB;   // inclusive
+  // inclusive; TAIL: no tile past the one that holds row S-1
+  const int t_max = TAIL ? min((qb * QB + QB - 1) / KB, t_tail)
+                         : (qb * QB + QB - 1) / KB;
   stage(t0, 0);
   __syncthreads();
 
@@ -364,7 +395,7 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
       for (int sub = 0; sub < 4; ++sub) {
         const int k0 = k0t + sub * 32;
         // skip: every key past every row of the wave, or before every bound
-        const bool live = (k0 <= w0 + WQ - 1) && (!DOC || k0 + 32 > lo_w0);
+        const bool live = (k0 <= w1) && (!DOC || k0 + 32 > lo_w0);
         if (live) {
           const bool cut = (k0 + 31 > w0) || (DOC && k0 < lo_w1);
           const f32x16 s = qk(sub);
@@ -388,20 +419,24 @@ __global__ __launch_bounds__(512, 2) void k_attn64_fwd(
   for (int r = 0; r < 16; ++r) {
     const int qr = (r & 3) + 8 * (r >> 2) + 4 * half;
     const float inv = 1.0f / __shfl(l_run, qr, 32);
-    const int64_t qg = (int64_t)w0 + qr;
-    Ob[qg * DH + col] = f2bf(oacc[0][r] * inv);
-    Ob[qg * DH + 32 + col] = f2bf(oacc[1][r] * inv);
+    const int64_t qg = (int64_t)w0r + qr;
+    if (!TAIL || qg < S) {
+      Ob[qg * DH + col] = f2bf(oacc[0][r] * inv);
+      Ob[qg * DH + 32 + col] = f2bf(oacc[1][r] * inv);
+    }
   }
-  if (half == 0) Lb[q_row] = 0.6931471805599453f * (m_run + __log2f(l_run));
+  if (half == 0 && (!TAIL || w0r + col < S))
+    Lb[w0r + col] = 0.6931471805599453f * (m_run + __log2f(l_run));
 }
 
 // ============================================================================
 // Backward preprocess: delta = rowsum(dO*O), lse2 = LSE*log2e and, with SINK,
 //   part[bh*nblk + blk] = -sum_{rows of the block} exp(sink - LSE) * delta.
 // Grid (S/256, B*Hq), 4 waves; a row is 8 lanes x 16 B, a wave takes 8 rows
-// per pass. Every sum runs in a fixed order.
+// per pass. Every sum runs in a fixed order. TAIL: grid ceil(S/256); a row
+// >= S reads row S-1, stores nothing and adds 0 to the partial.
 // ============================================================================
-template <bool SINK>
+template <bool SINK, bool TAIL>
 __global__ __launch_bounds__(256) void k_attn64_bwd_pre(
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O,
     const float* __restrict__ LSE, const float* __restrict__ sinks,
@@ -416,7 +451,9 @@ __global__ __launch_bounds__(256) void k_attn64_bwd_pre(
   const float sink = SINK ? sinks[bh % Hq] : 0.f;
   float gacc = 0.f;   // this 8-lane group's share, the same in its lanes
   for (int it = 0; it < 8; ++it) {
-    const int64_t r = bh * S + (int64_t)blockIdx.x * 256 + it * 32 + wave * 8 + grp;
+    const int64_t sr = (int64_t)blockIdx.x * 256 + it * 32 + wave * 8 + grp;
+    const bool ok = !TAIL || sr < S;
+    const int64_t r = bh * S + (TAIL ? min(sr, S - 1) : sr);
     const bf16x8 a = reinterpret_cast<const bf16x8*>(dO + r * DH)[cl];
     const bf16x8 o = reinterpret_cast<const bf16x8*>(O + r * DH)[cl];
     float acc = 0.f;
@@ -425,11 +462,11 @@ __global__ __launch_bounds__(256) void k_attn64_bwd_pre(
 #pragma unroll
     for (int x = 4; x > 0; x >>= 1) acc += __shfl_xor(acc, x, kWave);
     const float lse = LSE[r];
-    if (cl == 0) {
+    if (cl == 0 && ok) {
       delta[r] = acc;
       lse2[r] = lse * LOG2E;
     }
-    if (SINK) gacc += expf(sink - lse) * acc;
+    if (SINK) gacc += ok ? expf(sink - lse) * acc : 0.f;
   }
   if (SINK) {
     float g[8];
@@ -469,7 +506,11 @@ __global__ void k_attn64_dsinks(const float* __restrict__ part,
 // ============================================================================
 constexpr int DKV_STAGE = 32768 + 1536;
 
-template <bool DOC>
+// TAIL: strip rows >= S read K / V row S-1 and are not stored; the q tile
+// that holds row S-1 is staged with clamped sources (Q, dO, lse2, delta, lo)
+// and its rows >= S get P = dS = 0 through a row < S term in the masked body,
+// which every quadrant that reaches S takes.
+template <bool DOC, bool TAIL>
 __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
@@ -497,12 +538,14 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
   const int kv0 = kvb * 64;
   const int kvs0 = kv0 + kvslice * 32;          // the wave's first kv row
   const int64_t kvbase = (((int64_t)b * Hkv + hkv) * S) * DH;
+  const int sm1 = (int)S - 1;
 
   // the slice's K / V B-fragments: row kvs0 + col, chunk c*16 + half*8
   bf16frag kf[4], vf[4];
+  const int kv_ld = TAIL ? min(kvs0 + col, sm1) : kvs0 + col;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const int64_t o = kvbase + (int64_t)(kvs0 + col) * DH + c * 16 + half * 8;
+    const int64_t o = kvbase + (int64_t)kv_ld * DH + c * 16 + half * 8;
     kf[c] = *reinterpret_cast<const bf16frag*>(K + o);
     vf[c] = *reinterpret_cast<const bf16frag*>(V + o);
   }
@@ -513,11 +556,13 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
 
   const float scale2 = scale * LOG2E;
   const int qt0 = kv0 / 128;           // 128-row q tiles
-  int qtn = (int)(S / 128);
+  int qtn = (int)((S + (TAIL ? 127 : 0)) / 128);
   int hi_w = 0;
   if (DOC) {
-    qtn = (hi[kv0 + 63] + 127) / 128;                           // block end
-    hi_w = __builtin_amdgcn_readfirstlane(hi[kvs0 + 31]);       // wave end
+    const int j_b = TAIL ? min(kv0 + 63, sm1) : kv0 + 63;
+    const int j_w = TAIL ? min(kvs0 + 31, sm1) : kvs0 + 31;
+    qtn = (hi[j_b] + 127) / 128;                                // block end
+    hi_w = __builtin_amdgcn_readfirstlane(hi[j_w]);             // wave end
   }
   const int ntiles = qtn - qt0;
   const int itn = rep * ntiles;
@@ -525,29 +570,45 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
   uint32_t ssrc[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) ssrc[u] = img_src(wave * 4 + u, lane);
+  // TAIL: the lane offsets of the q tile that holds row S-1
+  const int qt_tail = TAIL ? sm1 / 128 : 0;
+  uint32_t ssrc_t[4] = {0, 0, 0, 0};
+  uint32_t st_t[2] = {0, 0};
+  if (TAIL) {
+    const int rmax = sm1 - qt_tail * 128;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      ssrc_t[u] = img_src_tail(wave * 4 + u, lane, rmax);
+    st_t[0] = (uint32_t)min(lane, rmax);
+    st_t[1] = (uint32_t)min(64 + lane, rmax);
+  }
   // stage (head g, q tile) number `it` into buffer `buf`
   auto stage = [&](int it, int buf) __attribute__((always_inline)) {
     const int g = it / ntiles;
     const int qt = qt0 + (it - g * ntiles);
     const int64_t rowbase = ((int64_t)b * Hq + hkv * rep + g) * S + (int64_t)qt * 128;
     char* sb = smem + buf * DKV_STAGE;
+    const bool tl = TAIL && qt == qt_tail;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      glds16a(Q + rowbase * DH + ssrc[u],
+      const uint32_t so = tl ? ssrc_t[u] : ssrc[u];
+      glds16a(Q + rowbase * DH + so,
               reinterpret_cast<bf16_t*>(sb) + (wave * 4 + u) * 512);
-      glds16a(dO + rowbase * DH + ssrc[u],
+      glds16a(dO + rowbase * DH + so,
               reinterpret_cast<bf16_t*>(sb + 16384) + (wave * 4 + u) * 512);
     }
     float* st = reinterpret_cast<float*>(sb + 32768);
+    const uint32_t s0 = tl ? st_t[0] : (uint32_t)lane;
+    const uint32_t s1 = tl ? st_t[1] : 64 + (uint32_t)lane;
     if (wave == 0) {
-      glds4(lse2 + rowbase + (uint32_t)lane, st);
-      glds4(lse2 + rowbase + 64 + (uint32_t)lane, st + 64);
+      glds4(lse2 + rowbase + s0, st);
+      glds4(lse2 + rowbase + s1, st + 64);
     } else if (wave == 1) {
-      glds4(delta + rowbase + (uint32_t)lane, st + 128);
-      glds4(delta + rowbase + 64 + (uint32_t)lane, st + 192);
+      glds4(delta + rowbase + s0, st + 128);
+      glds4(delta + rowbase + s1, st + 192);
     } else if (DOC && wave == 2) {
-      glds4(lo + qt * 128 + (uint32_t)lane, st + 256);
-      glds4(lo + qt * 128 + 64 + (uint32_t)lane, st + 320);
+      glds4(lo + qt * 128 + s0, st + 256);
+      glds4(lo + qt * 128 + s1, st + 320);
     }
   };
 
@@ -573,9 +634,11 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
     for (int j = 0; j < 2; ++j) {
       const int rl0 = qh * 64 + j * 32;        // quadrant's first image row
       const int q0 = qt * 128 + rl0;
-      const bool live = (q0 + 31 >= kvs0) && (!DOC || q0 < hi_w);
+      const bool live = (q0 + 31 >= kvs0) && (!DOC || q0 < hi_w) &&
+                        (!TAIL || q0 <= sm1);
       if (!live) continue;
       bool cut = q0 < kvs0 + 31;
+      if (TAIL) cut = cut || (q0 + 31 > sm1);
       if (DOC)
         cut = cut || __builtin_amdgcn_readfirstlane(
                          reinterpret_cast<const int*>(stat)[256 + rl0 + 31]) > kvs0;
@@ -599,6 +662,8 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
         // past that row or before the row's lower bound
         const int c_lim = (kvs0 + col) - q0 - 4 * half;
         const int kv_abs = kvs0 + col;
+        // TAIL: q row q0 + idx + 4*half is >= S
+        const int r_lim = (int)S - q0 - 4 * half;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           const int qr4 = rl0 + 8 * jj + 4 * half;
@@ -624,6 +689,7 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
               if (MASK) {
                 bool masked = (i + 8 * jj) < c_lim;
                 if (DOC) masked = masked || (kv_abs < lo_q[i]);
+                if (TAIL) masked = masked || ((i + 8 * jj) >= r_lim);
                 pp = masked ? 0.f : pp;
               }
               pv[rr] = pp;
@@ -678,8 +744,10 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
       _Pragma("unroll") for (int r = 0; r < 16; ++r) {                        \
         const int kvr = (r & 3) + 8 * (r >> 2) + 4 * half;                    \
         const int64_t o = kvbase + (int64_t)(kvs0 + kvr) * DH + col;          \
-        DST[o] = f2bf(ACC[0][r] + slot[r]);                                   \
-        DST[o + 32] = f2bf(ACC[1][r] + slot[16 + r]);                         \
+        if (!TAIL || kvs0 + kvr < S) {                                        \
+          DST[o] = f2bf(ACC[0][r] + slot[r]);                                 \
+          DST[o + 32] = f2bf(ACC[1][r] + slot[16 + r]);                       \
+        }                                                                     \
       }                                                                       \
     }                                                                         \
     __syncthreads();                                                          \
@@ -696,7 +764,9 @@ __global__ __launch_bounds__(256, 2) void k_attn64_bwd_dkv(
 // the K image feeds both S = K Q^T (b128 A-fragments) and dQ += dS^T K (tr16
 // B-fragments). Each 32-key subtile has its own wave-uniform live / cut test.
 // ============================================================================
-template <bool DOC>
+// TAIL: as the forward: rows >= S compute row S-1 and are not stored, the kv
+// loop ends at the tile that holds row S-1, staged with clamped sources.
+template <bool DOC, bool TAIL>
 __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
@@ -723,8 +793,12 @@ __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
   const bf16_t* Vb = V + (((int64_t)b * Hkv + hkv) * S) * DH;
 
   const int q0b = qb * 128;
-  const int w0 = q0b + wave * 32;      // the wave's first q row
-  const int q_l = w0 + col;            // this lane's q row
+  const int w0r = q0b + wave * 32;     // the wave's first q row
+  const int sm1 = (int)S - 1;
+  // rows the wave and the lane compute (TAIL: clamped to S-1)
+  const int w0 = TAIL ? min(w0r, sm1) : w0r;
+  const int w1 = TAIL ? min(w0r + 31, sm1) : w0r + 31;
+  const int q_l = TAIL ? min(w0r + col, sm1) : w0r + col;
 
   bf16frag qrow[4], dorow[4];
 #pragma unroll
@@ -741,7 +815,7 @@ __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
   if (DOC) {
     lo_l = lo[q_l];
     lo_w0 = __builtin_amdgcn_readfirstlane(lo[w0]);
-    lo_w1 = __builtin_amdgcn_readfirstlane(lo[w0 + 31]);
+    lo_w1 = __builtin_amdgcn_readfirstlane(lo[w1]);
     kvt_begin = lo[q0b] / 64;
   }
 
@@ -752,13 +826,22 @@ __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
   uint32_t ssrc[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) ssrc[u] = img_src(wave * 2 + u, lane);
+  // TAIL: the lane offsets of the kv tile that holds row S-1
+  const int kt_tail = TAIL ? sm1 / 64 : 0;
+  uint32_t ssrc_t[2] = {0, 0};
+  if (TAIL) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      ssrc_t[u] = img_src_tail(wave * 2 + u, lane, sm1 - kt_tail * 64);
+  }
   auto stage = [&](int kvt, int buf) __attribute__((always_inline)) {
     char* sb = smem + buf * 16384;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      glds16a(Kb + (int64_t)kvt * 64 * DH + ssrc[u],
+      const uint32_t so = (TAIL && kvt == kt_tail) ? ssrc_t[u] : ssrc[u];
+      glds16a(Kb + (int64_t)kvt * 64 * DH + so,
               reinterpret_cast<bf16_t*>(sb) + (wave * 2 + u) * 512);
-      glds16a(Vb + (int64_t)kvt * 64 * DH + ssrc[u],
+      glds16a(Vb + (int64_t)kvt * 64 * DH + so,
               reinterpret_cast<bf16_t*>(sb + 8192) + (wave * 2 + u) * 512);
     }
   };
@@ -768,7 +851,8 @@ __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
 #pragma unroll
   for (int d = 0; d < 2; ++d) tr_offsets(lane, d, troff[d][0], troff[d][1]);
 
-  const int kvtn = (q0b + 128) / 64;   // exclusive
+  // exclusive; TAIL: no tile past the one that holds row S-1
+  const int kvtn = TAIL ? min((q0b + 128) / 64, kt_tail + 1) : (q0b + 128) / 64;
   stage(kvt_begin, 0);
   __syncthreads();
   int cur = 0;
@@ -780,7 +864,7 @@ __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       const int k0 = kvt * 64 + sub * 32;
-      const bool live = (k0 <= w0 + 31) && (!DOC || k0 + 32 > lo_w0);
+      const bool live = (k0 <= w1) && (!DOC || k0 + 32 > lo_w0);
       if (!live) continue;
       const bool cut = (k0 + 31 > w0) || (DOC && k0 < lo_w1);
 
@@ -841,16 +925,18 @@ __global__ __launch_bounds__(256, 3) void k_attn64_bwd_dq(
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qr = (r & 3) + 8 * (r >> 2) + 4 * half;
-    const int64_t o = (qbase + w0 + qr) * DH + col;
-    dQ[o] = f2bf(dq2[0][r]);
-    dQ[o + 32] = f2bf(dq2[1][r]);
+    const int64_t o = (qbase + w0r + qr) * DH + col;
+    if (!TAIL || w0r + qr < S) {
+      dQ[o] = f2bf(dq2[0][r]);
+      dQ[o + 32] = f2bf(dq2[1][r]);
+    }
   }
 }
 
 // shared argument checks
 int check_common(int B, int Hq, int Hkv, int64_t S, float scale) {
   VH_CHECK(B > 0 && Hq > 0 && Hkv > 0, "B, Hq, Hkv must be > 0");
-  VH_CHECK(S > 0 && S % 256 == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(S > 0, "S must be > 0");
   VH_CHECK(S * DH < (1ll << 31), "S too large for 32-bit tile offsets");
   VH_CHECK(Hq % Hkv == 0, "Hq %% Hkv != 0");
   VH_CHECK(scale > 0, "scale must be > 0 (got %g)", (double)scale);
@@ -866,17 +952,27 @@ extern "C" int vh_attn64_fwd_bf16(const uint16_t* Q, const uint16_t* K,
                                   const float* sinks, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (int rc = check_common(B, Hq, Hkv, S, scale)) return rc;
-  dim3 grid((uint32_t)(S / QB), (uint32_t)(B * Hq));
+  dim3 grid((uint32_t)((S + QB - 1) / QB), (uint32_t)(B * Hq));
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, dim3(512), 65536, s, Q, K, V, O, LSE, lo, B,
                        Hq, Hkv, S, scale, sinks);
   };
-  if (sinks) {
-    if (lo) launch(k_attn64_fwd<true, true>);
-    else launch(k_attn64_fwd<false, true>);
+  if (S % 256 == 0) {
+    if (sinks) {
+      if (lo) launch(k_attn64_fwd<true, true, false>);
+      else launch(k_attn64_fwd<false, true, false>);
+    } else {
+      if (lo) launch(k_attn64_fwd<true, false, false>);
+      else launch(k_attn64_fwd<false, false, false>);
+    }
   } else {
-    if (lo) launch(k_attn64_fwd<true, false>);
-    else launch(k_attn64_fwd<false, false>);
+    if (sinks) {
+      if (lo) launch(k_attn64_fwd<true, true, true>);
+      else launch(k_attn64_fwd<false, true, true>);
+    } else {
+      if (lo) launch(k_attn64_fwd<true, false, true>);
+      else launch(k_attn64_fwd<false, false, true>);
+    }
   }
   VH_HIP(hipGetLastError());
   return 0;
@@ -888,21 +984,25 @@ extern "C" int vh_attn64_bwd_pre_bf16(const uint16_t* dO, const uint16_t* O,
                                       float* partials, int B, int Hq,
                                       int64_t S, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  VH_CHECK(S > 0 && S % 256 == 0, "S %% 256 != 0 (pad the sequence)");
+  VH_CHECK(S > 0, "S must be > 0");
   VH_CHECK(B > 0 && Hq > 0, "B, Hq must be > 0");
   VH_CHECK(sinks == nullptr || (dsinks != nullptr && partials != nullptr),
            "sinks need the dsinks output and the partials workspace");
-  const int nblk = (int)(S / 256);
+  const int nblk = (int)((S + 255) / 256);
   dim3 grid((uint32_t)nblk, (uint32_t)(B * Hq));
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, dO, O, LSE, sinks, delta,
+                       lse2, partials, S, Hq);
+  };
   if (sinks) {
-    hipLaunchKernelGGL(k_attn64_bwd_pre<true>, grid, dim3(256), 0, s, dO, O,
-                       LSE, sinks, delta, lse2, partials, S, Hq);
+    if (S % 256 == 0) launch(k_attn64_bwd_pre<true, false>);
+    else launch(k_attn64_bwd_pre<true, true>);
     VH_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_attn64_dsinks, dim3((Hq + 63) / 64), dim3(64), 0, s,
                        partials, dsinks, B, Hq, nblk);
   } else {
-    hipLaunchKernelGGL(k_attn64_bwd_pre<false>, grid, dim3(256), 0, s, dO, O,
-                       LSE, sinks, delta, lse2, partials, S, Hq);
+    if (S % 256 == 0) launch(k_attn64_bwd_pre<false, false>);
+    else launch(k_attn64_bwd_pre<false, true>);
   }
   VH_HIP(hipGetLastError());
   return 0;
@@ -918,8 +1018,8 @@ extern "C" int vh_attn64_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (int rc = check_common(B, Hq, Hkv, S, scale)) return rc;
   VH_CHECK((lo == nullptr) == (hi == nullptr), "lo/hi must be passed together");
-  dim3 grid_kv((uint32_t)(S / 64), (uint32_t)(B * Hkv));
-  dim3 grid_q((uint32_t)(S / 128), (uint32_t)(B * Hq));
+  dim3 grid_kv((uint32_t)((S + 63) / 64), (uint32_t)(B * Hkv));
+  dim3 grid_q((uint32_t)((S + 127) / 128), (uint32_t)(B * Hq));
   auto launch_dkv = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid_kv, dim3(256), 2 * DKV_STAGE, s, Q, K, V, dO,
                        delta, lse2, dK, dV, lo, hi, B, Hq, Hkv, S, scale);
@@ -928,11 +1028,22 @@ extern "C" int vh_attn64_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
     hipLaunchKernelGGL(kern, grid_q, dim3(256), 32768, s, Q, K, V, dO, delta,
                        lse2, dQ, lo, B, Hq, Hkv, S, scale);
   };
-  if (lo) launch_dkv(k_attn64_bwd_dkv<true>);
-  else launch_dkv(k_attn64_bwd_dkv<false>);
+  const bool tail = S % 256 != 0;
+  if (tail) {
+    if (lo) launch_dkv(k_attn64_bwd_dkv<true, true>);
+    else launch_dkv(k_attn64_bwd_dkv<false, true>);
+  } else {
+    if (lo) launch_dkv(k_attn64_bwd_dkv<true, false>);
+    else launch_dkv(k_attn64_bwd_dkv<false, false>);
+  }
   VH_HIP(hipGetLastError());
-  if (lo) launch_dq(k_attn64_bwd_dq<true>);
-  else launch_dq(k_attn64_bwd_dq<false>);
+  if (tail) {
+    if (lo) launch_dq(k_attn64_bwd_dq<true, true>);
+    else launch_dq(k_attn64_bwd_dq<false, true>);
+  } else {
+    if (lo) launch_dq(k_attn64_bwd_dq<true, false>);
+    else launch_dq(k_attn64_bwd_dq<false, false>);
+  }
   VH_HIP(hipGetLastError());
   return 0;
 }

@@ -876,7 +876,7 @@ def attn_bwd_token_major(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 
 def _check_window_sinks(B, Hq, S, D, device, lo, hi, sinks):
-    assert D == 128 and S % 256 == 0, (S, D)
+    assert D == 128 and S >= 1, (S, D)
     for t in (lo, hi):
         assert t is None or (t.dtype == torch.int32 and t.shape == (S,)
                              and t.is_contiguous() and t.device == device), \
@@ -895,10 +895,11 @@ def attn_fwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     (vh_attn_fwd_win_sink_bf16). lo: int32 [S] first visible key per row,
     shared by the batch (ops.kernels.attention.window_bounds); sinks: fp32
     [Hq] logits of the extra softmax column. Returns (o, lse); lse includes
-    the sink."""
+    the sink. Any S >= 1 (head-major; token_major needs S % 256 == 0)."""
     B, Hq, S, D = q.shape
     Hkv = k.shape[1]
     _check_window_sinks(B, Hq, S, D, q.device, lo, None, sinks)
+    assert not token_major or S % 256 == 0, (S, token_major)
     if token_major:
         o = torch.empty(B, S, Hq, D, dtype=q.dtype, device=q.device)
         strides = _bhs_strides(o.transpose(1, 2))
@@ -928,6 +929,7 @@ def attn_bwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     Hkv = k.shape[1]
     _check_window_sinks(B, Hq, S, D, q.device, lo, hi, sinks)
     assert (lo is None) == (hi is None)
+    assert not token_major or S % 256 == 0, (S, token_major)
     if token_major:
         assert o.shape == (B, S, Hq, D) and o.is_contiguous(), (o.shape, o.stride())
         strides = _bhs_strides(o.transpose(1, 2))
@@ -943,7 +945,8 @@ def attn_bwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     dsinks = part = None
     if sinks is not None:
         dsinks = torch.empty(Hq, dtype=torch.float32, device=dev)
-        part = torch.empty(B * Hq * (S // 256), dtype=torch.float32, device=dev)
+        part = torch.empty(B * Hq * ((S + 255) // 256), dtype=torch.float32,
+                           device=dev)
     lib = get_lib()
     with _prof("attn_bwd", 3.0 * 2 * 2 * S * S * Hq * D * 0.5 * B):
         check(lib.vh_attn_bwd_pre_sink_bf16(
@@ -967,7 +970,7 @@ def attn_bwd_win_sink(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 def _check_attn64(q, k, v, lo, hi, sinks):
     B, Hq, S, D = q.shape
-    assert D == 64 and S % 256 == 0, (S, D)
+    assert D == 64 and S >= 1, (S, D)
     assert k.shape == v.shape and k.shape[0] == B and k.shape[2:] == (S, D) \
         and Hq % k.shape[1] == 0, (q.shape, k.shape, v.shape)
     for t in (q, k, v):
@@ -1026,7 +1029,8 @@ def attn64_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     dsinks = part = None
     if sinks is not None:
         dsinks = torch.empty(Hq, dtype=torch.float32, device=dev)
-        part = torch.empty(B * Hq * (S // 256), dtype=torch.float32, device=dev)
+        part = torch.empty(B * Hq * ((S + 255) // 256), dtype=torch.float32,
+                           device=dev)
     lib = get_lib()
     with _prof("attn_bwd", 3.0 * 2 * 2 * S * S * Hq * D * 0.5 * B):
         check(lib.vh_attn64_bwd_pre_bf16(

@@ -200,13 +200,14 @@ class _HipFlashAttention(torch.autograd.Function):
     """In-repo CDNA4 flash kernel pair (vh_attn_fwd_bf16 / vh_attn_bwd2_bf16;
     csrc/vh_attention.hip), and its head_dim 64 twin (vh_attn64_*;
     csrc/vh_attention64.hip), picked by q.shape[-1]. Causal, GQA, D in
-    {128, 64}, S % 256 == 0, bf16; optional
+    {128, 64}, any S >= 1, bf16; optional
     packed-varlen block-diagonal masking via per-token document bounds
     (the reference's flash-attn cu_seqlens path, attention/flash.py:61-91).
     sinks (fp32 [Hq], differentiable) and shared_bounds (doc_start / doc_end
     are key-window bounds shared by the batch, B > 1 allowed) go through the
-    vh_attn_*_win_sink entry points; without either the calls are the ones
-    above, unchanged.
+    vh_attn_*_win_sink entry points, and so does every head-major D = 128
+    call with S % 256 != 0 (that set has the tail-capable kernels); without
+    any of the three the calls are the ones above, unchanged.
 
     Parity-tested against torch autograd (tests/test_gpu_kernels.py). The
     attention slot dispatches this pair by default since round 2 (the GQA-
@@ -231,7 +232,8 @@ class _HipFlashAttention(torch.autograd.Function):
             ctx.scale = scale
             ctx.docs = (doc_start, doc_end)
             return o
-        ctx.win_sink = sinks is not None or shared_bounds
+        ctx.win_sink = sinks is not None or shared_bounds \
+            or q.shape[2] % 256 != 0
         if ctx.win_sink:
             assert (doc_start is None) == (doc_end is None)
             sk = sinks.detach().contiguous() if sinks is not None else None
@@ -286,7 +288,8 @@ def hip_flash_attention(q, k, v, scale, doc_start=None, doc_end=None,
     sinks: [h] attention-sink logits, differentiable.
     shared_bounds: doc_start / doc_end already are window bounds shared by
     the batch (what sliding_window builds).
-    D is 128 or 64; token_major needs D = 128."""
+    D is 128 or 64, S any length >= 1; token_major needs D = 128 and
+    S % 256 == 0."""
     S = q.shape[2]
     if q.shape[-1] not in (64, 128):
         raise ValueError(f"hip_flash_attention: head_dim must be 64 or 128, "
@@ -294,6 +297,9 @@ def hip_flash_attention(q, k, v, scale, doc_start=None, doc_end=None,
     if q.shape[-1] == 64 and token_major:
         raise ValueError("hip_flash_attention: token_major output is "
                          "implemented for head_dim 128 only")
+    if token_major and S % 256 != 0:
+        raise ValueError("hip_flash_attention: token_major output needs "
+                         f"S % 256 == 0, got S = {S}")
     if doc_start is not None and not shared_bounds:
         assert q.shape[0] == 1, "packed varlen requires B == 1"
     if check_sliding_window(sliding_window) is not None:
@@ -356,10 +362,9 @@ def hip_attention_forward(module, query, key, value, attention_mask,
                                                   q.shape[2])
     core = kwargs.get("core", _DEFAULT_CORE)
     if core == "hip_flash" and (q.shape[-1] not in (64, 128)
-                                or q.shape[2] % 256 != 0
                                 or q.dtype != torch.bfloat16):
-        # the in-repo pairs cover D in {128, 64}, S % 256, bf16; toy/unit
-        # shapes take the torch core (a dispatch policy, not a
+        # the in-repo pairs cover D in {128, 64}, any S, bf16; other head
+        # dims and fp32 take the torch core (a dispatch policy, not a
         # missing-extension fallback)
         core = "sdpa"
     if core == "hip_flash":
@@ -370,7 +375,7 @@ def hip_attention_forward(module, query, key, value, attention_mask,
                                   sliding_window=sliding_window)
     elif sliding_window is not None or s_aux is not None:
         # explicit window / document mask plus the sink column. This is the
-        # core that D outside {64, 128}, S % 256 != 0 and fp32 take.
+        # core that D outside {64, 128} and fp32 take.
         if scaling is None:
             scaling = q.shape[-1] ** -0.5
         lo, _ = window_bounds(q.shape[2], sliding_window, doc_start, doc_end,

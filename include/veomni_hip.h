@@ -478,6 +478,34 @@ int vh_attn64_bwd2_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V,
                         float scale, const int32_t* lo, const int32_t* hi,
                         void* stream);
 
+/* MLA flash pair (csrc/vh_attention_mla.hip): the causal flash pair for
+ * multi-head latent attention as it is trained, q / k heads 192 wide (128
+ * nope + 64 rope) and v heads 128 wide, bf16, head-major: Q, dQ [B,Hq,S,192],
+ * K, dK [B,Hkv,S,192], V, dV [B,Hkv,S,128], O, dO [B,Hq,S,128]; V is never
+ * padded. The lo / hi contract of the D = 64 set (nullable; int32 [S],
+ * monotone, shared by every batch row; row q sees keys lo[q] .. q, key j is
+ * seen by rows j .. hi[j]-1); no sinks.
+ * fwd: O, LSE [B,Hq,S] fp32. bwd_pre: delta, lse2 = LSE*log2e [B*Hq*S] (the
+ * D = 128 preprocess). bwd2: dQ, dK, dV each written once, no atomics,
+ * bit-identical from run to run; lo and hi both or neither.
+ * All three: any S >= 1 (S*192 < 2^31); fwd and bwd2: scale > 0,
+ * Hq % Hkv == 0, B*Hq < 65536. */
+int vh_attn_mla_fwd_bf16(const uint16_t* Q, const uint16_t* K,
+                         const uint16_t* V, uint16_t* O, float* LSE, int B,
+                         int Hq, int Hkv, int64_t S, float scale,
+                         const int32_t* lo, void* stream);
+
+int vh_attn_mla_bwd_pre_bf16(const uint16_t* dO, const uint16_t* O,
+                             const float* LSE, float* delta, float* lse2,
+                             int B, int Hq, int64_t S, void* stream);
+
+int vh_attn_mla_bwd2_bf16(const uint16_t* Q, const uint16_t* K,
+                          const uint16_t* V, const uint16_t* dO,
+                          const float* delta, const float* lse2, uint16_t* dQ,
+                          uint16_t* dK, uint16_t* dV, int B, int Hq, int Hkv,
+                          int64_t S, float scale, const int32_t* lo,
+                          const int32_t* hi, void* stream);
+
 /* Head dim 80 (csrc/vh_attention80.hip): NON-causal block-diagonal flash
  * attention for the vision tower, bf16, Hq == Hkv == H, no batch dimension.
  * Token-major operands: Q, K, V, dO are [S, H, 80] with the head stride

@@ -24,6 +24,7 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "vh_attention64.hip": _NO_PK_F32,
     "vh_attention80.hip": _NO_PK_F32,   # as vh_attention64.hip
+    "vh_attention_mla.hip": _NO_PK_F32,  # as vh_attention64.hip
     "vh_group_gemm8.hip": _NO_PK_F32,
 }
 
@@ -38,6 +39,7 @@ SOURCES = [
     "vh_attention.hip",
     "vh_attention64.hip",
     "vh_attention80.hip",
+    "vh_attention_mla.hip",
     "vh_ce.hip",
     "vh_logprob.hip",
     "vh_adamw.hip",

@@ -77,6 +77,15 @@ PRESETS = {
         moe_intermediate_size=64, router_aux_loss_coef=0.001,
         expert_style="gpt_oss", swiglu_limit=7.0,
     ),
+    # DeepSeek-V3 attention at test scale: multi-head latent attention with
+    # 192-wide q/k heads (128 nope + 64 rope) and 128-wide v heads, low-rank
+    # q and kv projections, dense MLP
+    "tiny-mla": ModelConfig(
+        name="tiny-mla", vocab_size=512, hidden_size=256, intermediate_size=512,
+        num_hidden_layers=2, num_attention_heads=4, num_key_value_heads=4,
+        attention_style="mla", q_lora_rank=96, kv_lora_rank=64,
+        qk_nope_head_dim=128, qk_rope_head_dim=64, v_head_dim=128,
+    ),
 }
 
 # VLM presets (VLConfig: text + vision towers), built via build_vl_model

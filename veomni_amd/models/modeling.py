@@ -84,9 +84,30 @@ class ModelConfig:
     attention_sinks: bool = False
     # multimodal (Qwen2.5-VL) 3D-RoPE channel sections (t, h, w); None = 1D
     mrope_section: Optional[tuple] = None
+    # "standard" = q/k/v projections with one head_dim; "mla" = DeepSeek
+    # multi-head latent attention (MLAttention): low-rank q and kv
+    # projections, q/k heads qk_nope_head_dim + qk_rope_head_dim wide, v heads
+    # v_head_dim wide. q_lora_rank None = a plain q_proj
+    attention_style: str = "standard"
+    q_lora_rank: Optional[int] = None
+    kv_lora_rank: int = 512
+    qk_nope_head_dim: int = 128
+    qk_rope_head_dim: int = 64
+    v_head_dim: int = 128
     name: str = "model"
 
     def __post_init__(self):
+        if self.attention_style not in ("standard", "mla"):
+            raise ValueError(
+                "attention_style must be 'standard' or 'mla', got "
+                f"{self.attention_style!r}")
+        if self.attention_style == "mla":
+            if self.qk_norm or self.attention_sinks or self.attention_bias:
+                raise ValueError(
+                    "attention_style='mla' has no qk_norm, attention_sinks "
+                    "or attention_bias")
+            # rope runs on the rope slice only (HF DeepseekV3Config)
+            self.head_dim = self.qk_rope_head_dim
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
         from ..ops.kernels.attention import check_sliding_window
@@ -473,6 +494,88 @@ class Attention(nn.Module):
         return out[None]
 
 
+class MLAttention(nn.Module):
+    """DeepSeek multi-head latent attention as it is trained (plain multi-head
+    attention after the low-rank projections; parameter names are HF
+    DeepseekV3Attention's, so state dicts load): q through q_proj, or q_a_proj
+    -> q_a_layernorm -> q_b_proj; kv_a_proj_with_mqa splits into the
+    compressed kv (-> kv_a_layernorm -> kv_b_proj -> k_nope, v per head) and
+    one shared rope key. Rope goes on the rope slices after the
+    interleave-to-half permutation, the rope key is expanded over the heads.
+    q/k heads are nope + rope wide and v heads v_head_dim wide; V is never
+    padded: the bound attention slot takes 192 / 128 as it is (the HIP MLA
+    flash pair, ops/kernels/attention.py)."""
+
+    def __init__(self, config: ModelConfig, layer_idx: int):
+        super().__init__()
+        self.config = config
+        self.layer_idx = layer_idx
+        self.num_heads = config.num_attention_heads
+        self.nope = config.qk_nope_head_dim
+        self.rope = config.qk_rope_head_dim
+        self.qk_head_dim = self.nope + self.rope
+        self.v_head_dim = config.v_head_dim
+        self.scaling = self.qk_head_dim ** -0.5
+        self.is_causal = True
+        self.sliding_window = config.layer_sliding_window(layer_idx)
+        H, nh = config.hidden_size, self.num_heads
+        if config.q_lora_rank is None:
+            self.q_proj = nn.Linear(H, nh * self.qk_head_dim, bias=False)
+        else:
+            self.q_a_proj = nn.Linear(H, config.q_lora_rank, bias=False)
+            self.q_a_layernorm = RMSNorm(config.q_lora_rank, eps=config.rms_norm_eps)
+            self.q_b_proj = nn.Linear(config.q_lora_rank, nh * self.qk_head_dim, bias=False)
+        self.kv_a_proj_with_mqa = nn.Linear(H, config.kv_lora_rank + self.rope, bias=False)
+        self.kv_a_layernorm = RMSNorm(config.kv_lora_rank, eps=config.rms_norm_eps)
+        self.kv_b_proj = nn.Linear(config.kv_lora_rank,
+                                   nh * (self.nope + self.v_head_dim), bias=False)
+        self.o_proj = nn.Linear(nh * self.v_head_dim, H, bias=False)
+
+    @staticmethod
+    def _rope_interleaved(x, cos, sin):
+        # pairs (2i, 2i+1) -> halves (i, i + d/2), then the rotate-half form
+        b, h, s, d = x.shape
+        x = x.view(b, h, s, d // 2, 2).transpose(4, 3).reshape(b, h, s, d)
+        return x * cos + rotate_half(x) * sin
+
+    def forward(self, hidden_states, position_embeddings, **kwargs):
+        ps = get_parallel_state()
+        if ps.ulysses_enabled and ps.async_ulysses:
+            raise NotImplementedError(
+                "async Ulysses does not support attention_style='mla'; use "
+                "the sync Ulysses path")
+        B, S = hidden_states.shape[:2]
+        nh = self.num_heads
+        if self.config.q_lora_rank is None:
+            q = self.q_proj(hidden_states)
+        else:
+            q = self.q_b_proj(self.q_a_layernorm(self.q_a_proj(hidden_states)))
+        q = q.view(B, S, nh, self.qk_head_dim).transpose(1, 2)
+        q_pass, q_rot = torch.split(q, [self.nope, self.rope], dim=-1)
+        ckv = self.kv_a_proj_with_mqa(hidden_states)
+        k_pass, k_rot = torch.split(ckv, [self.config.kv_lora_rank, self.rope], dim=-1)
+        kv = self.kv_b_proj(self.kv_a_layernorm(k_pass))
+        kv = kv.view(B, S, nh, self.nope + self.v_head_dim).transpose(1, 2)
+        k_pass, v = torch.split(kv, [self.nope, self.v_head_dim], dim=-1)
+        cos, sin = position_embeddings
+        cos, sin = cos.unsqueeze(1), sin.unsqueeze(1)
+        q_rot = self._rope_interleaved(q_rot, cos, sin)
+        k_rot = self._rope_interleaved(k_rot.reshape(B, 1, S, self.rope), cos, sin)
+        q = torch.cat((q_pass, q_rot), dim=-1)
+        k = torch.cat((k_pass, k_rot.expand(B, nh, S, self.rope)), dim=-1)
+        if self.sliding_window is not None:
+            kwargs = dict(kwargs, sliding_window=self.sliding_window)
+        if veomni_attention.use_non_eager_impl:
+            out, _ = veomni_attention(self, q, k, v, None, dropout=0.0,
+                                      scaling=self.scaling, **kwargs)
+        elif ps.ulysses_enabled:
+            out = Attention._sync_ulysses_attention(self, q, k, v, **kwargs)
+        else:
+            out, _ = sdpa_attention(self, q, k, v, None, dropout=0.0,
+                                    scaling=self.scaling, **kwargs)
+        return self.o_proj(out.reshape(B, S, -1).contiguous())
+
+
 class MLP(nn.Module):
     def __init__(self, config: ModelConfig):
         super().__init__()
@@ -702,7 +805,10 @@ class SparseMoeBlock(nn.Module):
 class DecoderLayer(nn.Module):
     def __init__(self, config: ModelConfig, layer_idx: int):
         super().__init__()
-        self.self_attn = Attention(config, layer_idx)
+        if config.attention_style == "mla":
+            self.self_attn = MLAttention(config, layer_idx)
+        else:
+            self.self_attn = Attention(config, layer_idx)
         self.mlp = SparseMoeBlock(config) if config.is_moe else MLP(config)
         self.input_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)

@@ -128,6 +128,12 @@ def get_lib() -> ctypes.CDLL:
          c_int, c_int, c_i64, c_p)
     _sig(lib, "vh_attn64_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
          c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
+    _sig(lib, "vh_attn_mla_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int,
+         c_int, c_i64, c_f32, c_p, c_p)
+    _sig(lib, "vh_attn_mla_bwd_pre_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_int,
+         c_i64, c_p)
+    _sig(lib, "vh_attn_mla_bwd2_bf16", c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+         c_p, c_int, c_int, c_int, c_i64, c_f32, c_p, c_p, c_p)
     _sig(lib, "vh_attn80_fwd_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_i64,
          c_i64, c_i64, c_f32, c_p, c_p, c_p)
     _sig(lib, "vh_attn80_bwd_pre_bf16", c_p, c_p, c_p, c_p, c_p, c_int, c_i64,
@@ -1049,6 +1055,74 @@ def attn64_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             dptr(hi) if hi is not None else None,
             cur_stream()), "vh_attn64_bwd2")
     return dq, dk, dv, dsinks
+
+
+def _check_attn_mla(q, k, v, lo, hi):
+    B, Hq, S, D = q.shape
+    assert D == 192 and S >= 1, (S, D)
+    Hkv = k.shape[1]
+    assert k.shape == (B, Hkv, S, 192) and v.shape == (B, Hkv, S, 128) \
+        and Hq % Hkv == 0, (q.shape, k.shape, v.shape)
+    for t in (q, k, v):
+        assert t.dtype == torch.bfloat16 and t.is_contiguous() \
+            and t.device == q.device and q.is_cuda, \
+            "q/k [B,H,S,192], v [B,H,S,128]: bf16, contiguous, on one GPU"
+    for t in (lo, hi):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (S,)
+                             and t.is_contiguous() and t.device == q.device), \
+            "bounds: int32 [S], contiguous, on the inputs' device"
+
+
+def attn_mla_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                 scale: float, lo: torch.Tensor | None = None):
+    """Causal GQA flash attention forward for MLA heads (vh_attn_mla_fwd_bf16):
+    q [B,Hq,S,192] bf16 contiguous, k [B,Hkv,S,192], v [B,Hkv,S,128]. lo: int32
+    [S] first visible key per row (document and/or window bounds, shared by
+    the batch). Returns (o [B,Hq,S,128], lse [B,Hq,S])."""
+    _check_attn_mla(q, k, v, lo, None)
+    B, Hq, S, _ = q.shape
+    o = torch.empty(B, Hq, S, 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+    with _prof("attn_fwd", 2.0 * S * S * Hq * (192 + 128) * 0.5 * B):
+        check(get_lib().vh_attn_mla_fwd_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(o), dptr(lse), B, Hq, k.shape[1], S,
+            scale, dptr(lo) if lo is not None else None,
+            cur_stream()), "vh_attn_mla_fwd")
+    return o, lse
+
+
+def attn_mla_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                 o: torch.Tensor, lse: torch.Tensor, do: torch.Tensor,
+                 scale: float, lo: torch.Tensor | None = None,
+                 hi: torch.Tensor | None = None):
+    """Backward for attn_mla_fwd. Returns (dq [B,Hq,S,192], dk [B,Hkv,S,192],
+    dv [B,Hkv,S,128]), each written once: the same bits from run to run."""
+    _check_attn_mla(q, k, v, lo, hi)
+    B, Hq, S, _ = q.shape
+    Hkv = k.shape[1]
+    assert (lo is None) == (hi is None)
+    assert o.shape == (B, Hq, S, 128) and o.is_contiguous() and o.dtype == q.dtype
+    assert do.shape == o.shape and do.dtype == q.dtype, (do.shape, do.dtype)
+    assert lse.shape == (B, Hq, S) and lse.dtype == torch.float32
+    do = do.contiguous()
+    dev = q.device
+    delta = torch.empty(B * Hq * S, dtype=torch.float32, device=dev)
+    lse2 = torch.empty(B * Hq * S, dtype=torch.float32, device=dev)
+    lib = get_lib()
+    with _prof("attn_bwd", 2.0 * S * S * Hq * (3 * 192 + 2 * 128) * 0.5 * B):
+        check(lib.vh_attn_mla_bwd_pre_bf16(
+            dptr(do), dptr(o), dptr(lse.contiguous()), dptr(delta), dptr(lse2),
+            B, Hq, S, cur_stream()), "vh_attn_mla_bwd_pre")
+        dq = torch.empty_like(q)
+        dk = torch.empty_like(k)
+        dv = torch.empty_like(v)
+        check(lib.vh_attn_mla_bwd2_bf16(
+            dptr(q), dptr(k), dptr(v), dptr(do), dptr(delta), dptr(lse2),
+            dptr(dq), dptr(dk), dptr(dv), B, Hq, Hkv, S, scale,
+            dptr(lo) if lo is not None else None,
+            dptr(hi) if hi is not None else None,
+            cur_stream()), "vh_attn_mla_bwd2")
+    return dq, dk, dv
 
 
 def _check_attn80(q, k, v, seg_lo, seg_hi):

@@ -6,7 +6,8 @@ seq-sharded/full-heads -> (a2a) -> full-seq/head-sharded -> kernel ->
 (a2a back); GQA KV head repeat when sp > kv heads.
 
 Core kernel (round 2+): the in-repo CDNA4 flash pairs (vh_attn_fwd_bf16 /
-vh_attn_bwd2_bf16 for head_dim 128, vh_attn64_* for head_dim 64) including
+vh_attn_bwd2_bf16 for head_dim 128, vh_attn64_* for head_dim 64,
+vh_attn_mla_* for q/k 192 with v 128) including
 the packed-varlen cu_seqlens path, key windows and sinks; torch SDPA
 (CK/AOTriton) remains as the A/B comparison core. The Ulysses layout
 exchanges are the §8a items and are implemented here.
@@ -35,6 +36,13 @@ _DEFAULT_CORE = os.environ.get("VEOMNI_ATTN_CORE", "hip_flash")
 # window, sinks or document bounds the torch core materialises S x S tensors,
 # and for plain single-document causal the pair measured faster forward+
 # backward than SDPA's own flash kernel (profiles/attn_d64_microbench.md).
+# The same holds for MLA heads (192 / 128): the pair measured faster than the
+# torch core and than the zero-padded-V recipe in every case, plain causal
+# included (profiles/attn_mla_microbench.md).
+
+
+# (q/k, v) head dims the in-repo flash pairs serve
+_FLASH_HEAD_DIMS = ((64, 64), (128, 128), (192, 128))
 
 
 def docs_from_cu_seqlens(cu: torch.Tensor, seq_len: int):
@@ -220,6 +228,18 @@ class _HipFlashAttention(torch.autograd.Function):
                 sinks=None, shared_bounds=False):
         from .. import hip_lib
         ctx.d64 = q.shape[-1] == 64
+        ctx.mla = (q.shape[-1], v.shape[-1]) == (192, 128)
+        if ctx.mla:
+            # MLA heads (csrc/vh_attention_mla.hip): one head-major call set,
+            # no sinks; saved and differentiated like the D = 64 branch
+            assert not token_major and sinks is None
+            assert (doc_start is None) == (doc_end is None)
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            o, lse = hip_lib.attn_mla_fwd(q, k, v, scale, doc_start)
+            ctx.save_for_backward(q, k, v, o, lse)
+            ctx.scale = scale
+            ctx.docs = (doc_start, doc_end)
+            return o
         if ctx.d64:
             # head_dim 64 (csrc/vh_attention64.hip): one head-major call set
             # for every case; saved and differentiated like win_sink below
@@ -261,6 +281,11 @@ class _HipFlashAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         from .. import hip_lib
+        if ctx.mla:
+            q, k, v, o, lse = ctx.saved_tensors
+            dq, dk, dv = hip_lib.attn_mla_bwd(q, k, v, o, lse, do, ctx.scale,
+                                              *ctx.docs)
+            return dq, dk, dv, None, None, None, None, None, None
         if ctx.d64:
             q, k, v, o, lse, sk = ctx.saved_tensors
             dq, dk, dv, dsinks = hip_lib.attn64_bwd(
@@ -289,11 +314,18 @@ def hip_flash_attention(q, k, v, scale, doc_start=None, doc_end=None,
     shared_bounds: doc_start / doc_end already are window bounds shared by
     the batch (what sliding_window builds).
     D is 128 or 64, S any length >= 1; token_major needs D = 128 and
-    S % 256 == 0."""
+    S % 256 == 0. MLA heads, q / k 192 wide and v 128 wide (output 128 wide),
+    take documents and windows the same way, without sinks or token_major."""
     S = q.shape[2]
-    if q.shape[-1] not in (64, 128):
-        raise ValueError(f"hip_flash_attention: head_dim must be 64 or 128, "
-                         f"got {q.shape[-1]}")
+    dims = (q.shape[-1], v.shape[-1])
+    if k.shape[-1] != dims[0] or dims not in _FLASH_HEAD_DIMS:
+        raise ValueError(
+            "hip_flash_attention: (q/k, v) head dims must be one of "
+            f"{_FLASH_HEAD_DIMS}, got q {q.shape[-1]}, k {k.shape[-1]}, "
+            f"v {v.shape[-1]}")
+    if dims == (192, 128) and (token_major or sinks is not None):
+        raise ValueError("hip_flash_attention: the 192 / 128 pair has no "
+                         "token_major output and no sinks")
     if q.shape[-1] == 64 and token_major:
         raise ValueError("hip_flash_attention: token_major output is "
                          "implemented for head_dim 128 only")
@@ -361,10 +393,13 @@ def hip_attention_forward(module, query, key, value, attention_mask,
         doc_start, doc_end = docs_from_cu_seqlens(kwargs["cu_seq_lens_q"],
                                                   q.shape[2])
     core = kwargs.get("core", _DEFAULT_CORE)
-    if core == "hip_flash" and (q.shape[-1] not in (64, 128)
-                                or q.dtype != torch.bfloat16):
-        # the in-repo pairs cover D in {128, 64}, any S, bf16; other head
-        # dims and fp32 take the torch core (a dispatch policy, not a
+    mla = (q.shape[-1], v.shape[-1]) == (192, 128)
+    if core == "hip_flash" and ((q.shape[-1], v.shape[-1]) not in _FLASH_HEAD_DIMS
+                                or q.dtype != torch.bfloat16
+                                or (mla and s_aux is not None)):
+        # the in-repo pairs cover (q/k, v) head dims (64, 64), (128, 128) and
+        # (192, 128), any S, bf16; other head dims, fp32 and 192 / 128 with
+        # sinks take the torch core (a dispatch policy, not a
         # missing-extension fallback)
         core = "sdpa"
     if core == "hip_flash":
